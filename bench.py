@@ -19,6 +19,14 @@ Launch: python bench.py [--gpus N --steps 10 --warmup 2]
           passes rank 0's line through;
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
           (WORLD_SIZE must equal --gpus).
+A plain run builds the index, warms up, times --steps searches and prints the
+line (value, ms_per_step, the scan's roofline from the timed steps' own HIP
+events).  --full adds the side legs, each a run of its own after the timed
+steps: pcie_inclusive, latency_nq1 / latency_nq1_f32 (N = 1) and the CPU leg
+(cpu_baseline, recall@10 against the exact oracle; --no-cpu skips it).
+--dump-outputs DIR writes the last timed step's results (rank 0: the merged
+lists every caller receives) as DIR/D.npy (float32 distances, nq x k) and
+DIR/I.npy (row ids as float64, exact below 2^53).
 --data clustered: a clustered corpus (unit-norm rows around one common
 direction, the shape of sentence embeddings) with fp32 queries that are NOT
 exact in the storage dtype -- the certification's hard case.
@@ -389,6 +397,18 @@ def read_pmc_traffic(cfg_name, n_local, nq, data="synthetic"):
         return None, None
 
 
+def dump_outputs(out_dir, D, I):
+    """--dump-outputs: what the last timed step returned to its caller, whole
+    (nq x k each: 0.8 MB on the default workload)."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    D = D.cpu().numpy() if hasattr(D, "cpu") else np.asarray(D)
+    I = I.cpu().numpy() if hasattr(I, "cpu") else np.asarray(I)
+    np.save(out_dir / "D.npy", np.ascontiguousarray(D, dtype=np.float32))
+    np.save(out_dir / "I.npy", np.ascontiguousarray(I, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -405,10 +425,18 @@ def main():
     ap.add_argument("--cpu-rows", type=int, default=1_000_000)
     ap.add_argument("--cpu-queries", type=int, default=0, help="fixed CPU sample (0: auto-size)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU baseline sample time")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline / recall leg")
-    ap.add_argument("--latency-calls", type=int, default=200, help="single-query host calls of the latency_nq1 leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs after the timed steps: pcie_inclusive, latency_nq1[_f32], "
+                         "cpu_baseline + recall against the exact CPU oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's D / I as DIR/D.npy (float32) and DIR/I.npy (float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline / recall leg")
+    ap.add_argument("--latency-calls", type=int, default=200,
+                    help="--full: single-query host calls of the latency_nq1 leg")
     ap.add_argument("--ranks-check", action="store_true", help=argparse.SUPPRESS)  # tests: report the rank, exit
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     plan = launch_plan(args.gpus, os.environ)
     if plan.startswith("error"):
@@ -488,6 +516,9 @@ def main():
     else:
         scan_avg_ms = scan_ms / max(launches, 1)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, D, I)
+
     value = nq * args.steps / elapsed
     # roofline of the dominant kernel (the fused scan): algorithmic work per launch
     flops = 2.0 * nq * n_local * d
@@ -550,7 +581,7 @@ def main():
         "dropped_candidate_ids_last_step": dropped,
         "roofline": roof,
     }
-    if world == 1:
+    if args.full and world == 1:
         # the reference's call form: host float32 queries in, host D / I out
         # (PCIe both ways), same index -- reported beside `value`, never as it
         try:
@@ -578,7 +609,7 @@ def main():
                 out["latency_nq1_f32"] = latency_nq1_f32(args.latency_calls, device)
         except Exception as e:  # noqa: BLE001
             log("latency_nq1_f32 leg failed:", e)
-    if rank == 0 and not args.no_cpu:
+    if args.full and rank == 0 and not args.no_cpu:
         nthreads = int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or len(os.sched_getaffinity(0))
         with Heartbeat("cpu leg (recall oracle, CPU baseline) running"):
             extra = cpu_baseline_and_recall(args, n_total, d, dtype, k, D, I, xq, nthreads, device)

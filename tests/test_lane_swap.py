@@ -32,7 +32,8 @@ def test_probe_builds():
 def test_lane_swaps_on_device():
     import torch  # noqa: F401  (one HIP runtime per process)
     if not LIB.exists():
-        pytest.fail(f"{LIB} missing: build it on the CPU first (tests/test_lane_swap.py::test_probe_builds)")
+        pytest.fail(f"{LIB} missing: build it first (__graft_entry__.build(), or on the CPU "
+                    "tests/test_lane_swap.py::test_probe_builds)")
     lib = ctypes.CDLL(str(LIB))
     rng = np.random.default_rng(4)
     keys = rng.integers(0, 9, 64).astype(np.float32)           # many duplicate keys: ties -> smaller id

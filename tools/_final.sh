@@ -12,7 +12,7 @@ if [ "$part" = 1 ]; then
   timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method thread tests -m gpu > $o/pytest.log 2>&1
   timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.log 2>&1
   bash tools/profile_scan.sh ${tag}_d
-  timeout -k 10 600 python -u bench.py > $o/bench_d.json 2> $o/bench_d.err
+  timeout -k 10 600 python -u bench.py --full > $o/bench_d.json 2> $o/bench_d.err
   P="python3 -u tools/latency_probe.py --k 10 --reps 300"
   timeout -k 10 120 $P --rows 100000 --dim 384 --dtype float32 >> $o/latency.jsonl 2>> $o/latency.err
   timeout -k 10 120 $P --rows 1000000 --dim 384 --dtype float32 >> $o/latency.jsonl 2>> $o/latency.err
@@ -21,8 +21,8 @@ else
   FX_PROFILE_MIN=1 bash tools/profile_scan.sh ${tag}_d2
   bash tools/profile_scan.sh ${tag}_e --config e --steps 3 --warmup 1
   bash tools/profile_scan.sh ${tag}_b --config b
-  timeout -k 10 600 python -u bench.py --config e --steps 5 --warmup 1 > $o/bench_e.json 2> $o/bench_e.err
-  timeout -k 10 300 python -u bench.py --config b > $o/bench_b.json 2> $o/bench_b.err
+  timeout -k 10 600 python -u bench.py --full --config e --steps 5 --warmup 1 > $o/bench_e.json 2> $o/bench_e.err
+  timeout -k 10 300 python -u bench.py --full --config b > $o/bench_b.json 2> $o/bench_b.err
   timeout -k 10 300 python -u tools/block_skew.py --config d > $o/skew_d.json 2> $o/skew_d.err
 fi
 echo "final $tag part $part done"

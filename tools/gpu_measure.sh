@@ -12,16 +12,16 @@ parts=${*:-e c sweep lat}
 for p in $parts; do
   case $p in
     e)
-      timeout -k 10 420 python -u bench.py --config e --steps 5 --warmup 1 > "$out/bench_e.json" 2> "$out/bench_e.err" ;;
+      timeout -k 10 420 python -u bench.py --full --config e --steps 5 --warmup 1 > "$out/bench_e.json" 2> "$out/bench_e.err" ;;
     c)
       timeout -k 10 420 python -u tools/bench_e2e.py > "$out/bench_c.json" 2> "$out/bench_c.err" ;;
     sweep)
       for cfg in d e b; do
         for nq in 1 16 64 256; do
-          timeout -k 10 240 python -u bench.py --config $cfg --nq $nq --no-cpu --steps 20 --warmup 3 \
+          timeout -k 10 240 python -u bench.py --full --config $cfg --nq $nq --no-cpu --steps 20 --warmup 3 \
             >> "$out/sweep_$cfg.jsonl" 2>> "$out/sweep.err"
           if [ $nq -le 32 ]; then
-            FX_SCAN_Q32=1 timeout -k 10 240 python -u bench.py --config $cfg --nq $nq --no-cpu --steps 20 --warmup 3 \
+            FX_SCAN_Q32=1 timeout -k 10 240 python -u bench.py --full --config $cfg --nq $nq --no-cpu --steps 20 --warmup 3 \
               >> "$out/sweep_${cfg}_q32.jsonl" 2>> "$out/sweep.err"
           fi
         done

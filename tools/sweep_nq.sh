@@ -7,10 +7,10 @@ out=gpurun_out/${1:-sweep}
 mkdir -p "$out"
 for cfg in d b e; do
   for nq in 1 16 64 256 1024; do
-    timeout -k 10 240 python -u bench.py --config $cfg --nq $nq --no-cpu --steps 20 --warmup 3 \
+    timeout -k 10 240 python -u bench.py --full --config $cfg --nq $nq --no-cpu --steps 20 --warmup 3 \
       >> "$out/sweep_$cfg.jsonl" 2>> "$out/sweep.err"
     if [ "$cfg" != e ] && [ $nq -ge 256 ]; then
-      FX_SCAN_PLACE=0 timeout -k 10 240 python -u bench.py --config $cfg --nq $nq --no-cpu --steps 20 --warmup 3 \
+      FX_SCAN_PLACE=0 timeout -k 10 240 python -u bench.py --full --config $cfg --nq $nq --no-cpu --steps 20 --warmup 3 \
         >> "$out/sweep_${cfg}_place0.jsonl" 2>> "$out/sweep.err"
     fi
   done
