@@ -13,6 +13,9 @@
  *                         rag_datastore_manager.py:173
  *   index.search(x, k)    faiss_store.py:64,         faiss_Index_search           fx_index_search
  *                         rag_datastore_manager.py:218
+ *   index.range_search    (score >= s filter of      faiss_Index_range_search     fx_index_range_search
+ *     (x, radius)          query.py:42,                                            + fx_index_range_result
+ *                          2-cli-rag-search.py:48)
  *   index.ntotal          faiss_store.py:53          faiss_Index_ntotal           fx_index_ntotal
  *   (re)IndexFlatL2(d)    faiss_store.py:126         faiss_Index_reset            fx_index_reset
  *   faiss.write_index     faiss_store.py:91,         faiss_write_index_fname      fx_index_write
@@ -112,7 +115,10 @@ int fx_index_set_stream(FxIndex* index, void* stream);
  * wherever it has the shape), "refine_waves" 4/8/16,
  * "convoy" 0/1 (k_scan_v5 blocks start their split where its running blocks
  * are), "convoy_every" 1/2/4/8,
- * "host_spin" 0/1.  None changes results, only
+ * "host_spin" 0/1, "range_cap" 0 (= 1,048,576) or 1 .. 2^30 (entries, 8 B
+ * each, the range_search candidate buffer starts with; a call whose scan
+ * emits more grows it to the emitted count and scans a second time; setting
+ * the option drops a grown buffer).  None changes results, only
  * speed.  Unknown name or out-of-range value: FX_E_ARG.  (The diagnostic
  * build libfx_index_diag.so adds test hooks -- "force_fallback",
  * "scan_dbg" -- that the product library does not have.) */
@@ -149,6 +155,31 @@ int fx_index_add(FxIndex* index, int64_t n, const void* x, int x_dtype, int x_me
  * smaller one is kept for the next). */
 int fx_index_search(FxIndex* index, int64_t nq, const void* q, int q_dtype, int q_mem,
                     int k, float* D, int64_t* I, int out_mem);
+
+/* index.range_search(x, radius) (faiss IndexFlat::range_search): for every
+ * query row of q[nq][d], every row y with D(q, y) < radius (L2 index;
+ * IP index: q.y > radius), both strict.  D is the library's exact distance
+ * (fp64 sum over the stored row, one rounding to fp32), compared as fp32
+ * with the fp32 radius: membership is exact, whatever the options.  lims is
+ * a host array of nq + 1: query i owns entries lims[i] .. lims[i+1] of the
+ * result, ordered by ascending row id (ids carry id_offset).  The result
+ * stays in index-owned device buffers until the next range search, reset or
+ * free; fx_index_range_result copies it out.  Blocks in both memory modes
+ * (it returns sizes).  NaN radius: FX_E_ARG.  L2 with radius <= 0, or an
+ * empty index: all-zero lims.  nq == 0: FX_OK (lims[0] = 0).  At most 2^31-1
+ * queries, and 2^31-1 pairs passing the MFMA filter, per call
+ * (FX_E_UNSUPPORTED beyond); FX_E_OOM when the buffers cannot be allocated;
+ * FX_E_INTEGRITY when a candidate word named a row outside [0, ntotal)
+ * (counted in fx_index_last_dropped_candidates; never in a correct build). */
+int fx_index_range_search(FxIndex* index, int64_t nq, const void* q, int q_dtype, int q_mem,
+                          float radius, int64_t* lims);
+/* Copy the last range search's lims[nq] results to caller buffers (host or
+ * device): D f32, I int64.  FX_E_ARG when no result is stored. */
+int fx_index_range_result(FxIndex* index, float* D, int64_t* I, int out_mem);
+/* Of the last range search: (query, row) pairs the MFMA scan emitted (>= the
+ * result count; the exact pass removed the rest) and scan passes run (1, or
+ * 2 when the candidate buffer had to grow; 0 when no scan was needed). */
+int fx_index_last_range_stats(FxIndex* index, int64_t* candidates, int* passes);
 
 /* Number of queries of the last search whose top-k could not be certified
  * from the scan's candidate margin and were re-scanned with a wide candidate

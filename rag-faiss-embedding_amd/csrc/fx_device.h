@@ -396,6 +396,35 @@ __device__ __forceinline__ void compact_full(float* lst_d, int* lst_i, int* cnt,
     }
 }
 
+// Builtin-MFMA fragments of the plain scans (k_scan_topk, k_range_scan): one
+// 16-B LDS read per lane and 64-B k-chunk, products summed onto c.
+template <int DT> struct Frag;
+template <> struct Frag<BF16> {
+    typedef bf16x8 T;
+    static __device__ __forceinline__ f32x4 mma(T a, T b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+};
+template <> struct Frag<F16> {
+    typedef f16x8 T;
+    static __device__ __forceinline__ f32x4 mma(T a, T b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    }
+};
+template <> struct Frag<F32> {
+    typedef f32x4 T;
+    // one 1-KiB fragment block holds 16 rows x 16 k: lane l has row l&15,
+    // k = 4(l>>4) .. 4(l>>4)+3.  MFMA step j sums k = 4c+j (c = l>>4): every
+    // k is covered exactly once; A and B use the same permutation.
+    static __device__ __forceinline__ f32x4 mma(T a, T b, f32x4 c) {
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
+        return c;
+    }
+};
+
 // f32: a 64-B k-chunk is 4 k-steps of 16x16x4 (see Frag<F32>); B is kept as 4
 // scalar AGPRs per chunk.
 struct Bf32 { float x[4]; };

@@ -79,6 +79,11 @@ struct DevBuf {
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
+// range_search's candidate buffer: entries it starts with unless the option
+// range_cap says otherwise (8 B each, plus 24 B per candidate actually found
+// for the exact distances, the sort and the result), and the option's limit
+constexpr int RANGE_CAP_DEFAULT = 1 << 20, RANGE_CAP_MAX = 1 << 30;
+
 // Per-index tuning options.  Initial values come from the FX_* environment
 // variables, read ONCE when the index is created (never on the search path);
 // fx_index_set_option changes them afterwards (range-checked: opt_range).
@@ -121,6 +126,8 @@ struct Options {
                              // are (ScanParams.conv); 0: at the split's first tile
     int convoy_every = 4;    // FX_CONVOY_EVERY: a block publishes its tile every this many tiles (1/2/4/8;
                              // 1: (d) 1.8x slower -- every block of a split writing one line each tile)
+    int range_cap = 0;       // FX_RANGE_CAP: entries the range_search candidate buffer starts with (0: the
+                             // default RANGE_CAP_DEFAULT; a call that finds more grows it and scans again)
     int host_spin = 1;       // FX_HOST_SPIN: a host-output search waits for its results by polling the
                              // stream (1) instead of a blocking hipStreamSynchronize (0)
 #ifdef FX_DIAG
@@ -158,6 +165,8 @@ struct Options {
         num("FX_CONVOY", convoy);
         num("FX_CONVOY_EVERY", convoy_every);
         num("FX_REFINE_WAVES", refine_waves);
+        num("FX_RANGE_CAP", range_cap);
+        if (range_cap < 0 || range_cap > RANGE_CAP_MAX) range_cap = 0;
         if (refine_waves != 4 && refine_waves != 8 && refine_waves != 16) refine_waves = REFINE_WG_WAVES;
         (void)str;
 #ifdef FX_DIAG
@@ -201,6 +210,7 @@ struct Options {
             {"convoy", &convoy, 0, 1, nullptr, 0},
             {"convoy_every", &convoy_every, 1, 8, nullptr, 0},
             {"refine_waves", &refine_waves, 4, 16, kWaves, 3},
+            {"range_cap", &range_cap, 0, RANGE_CAP_MAX, nullptr, 0},
 #ifdef FX_DIAG
             {"force_fallback", &force_fallback, 0, 2, nullptr, 0},
             {"scan_dbg", &scan_dbg, 0, 1 << 20, nullptr, 0},
@@ -319,6 +329,16 @@ struct FxIndex {
     // (a corrupted candidate list; 0 unless something is broken)
     int64_t last_dropped = 0;
     int* dev_drop = nullptr;  // its device word, zeroed at the start of every search
+    // range_search (fx_range.hip): its own query operands and thresholds (none
+    // of them a buffer a search graph captured), the candidate words, and the
+    // last call's result (lims / D / I), kept until the next range search,
+    // reset or free
+    DevBuf rg_qin, rg_qf32, rg_qop, rg_eps, rg_rho, rg_shift, rg_thr, rg_cnt, rg_cand, rg_dist, rg_sorted, rg_temp,
+        rg_lims, rg_D, rg_I;
+    int64_t rg_nq = -1;       // queries of the stored result (-1: none)
+    int64_t rg_total = 0;     // its lims[nq]
+    int64_t rg_cands = 0;     // pairs the MFMA scan emitted
+    int rg_passes = 0;        // scan passes run (0: no scan was needed)
     DevBuf conv;  // k_scan_v5 convoy words (CONV_WORDS; zeroed once, then only hints)
     int last_plan[3] = {0, 0, 0};  // the last search's scan plan: tile rows (128 k_scan_v4, 64 k_scan_v5), qt, splits
     // profiling
@@ -1258,7 +1278,9 @@ void fx_index_free(FxIndex* h) {
                           &h->fbc_d, &h->fbc_i, &h->stage, &h->gtau, &h->trace, &h->dbgbuf, &h->split, &h->cnorms,
                           &h->centre, &h->mu_part, &h->qshift, &h->qrho, &h->stamps, &h->pub, &h->cand2_d,
                           &h->cand2_i, &h->rq_f32, &h->rq_op, &h->rq_eps, &h->rq_rho, &h->rq_shift, &h->rq_gtau,
-                          &h->rq_cand_d, &h->rq_cand_i, &h->rq_flag, &h->hk_ws, &h->hout, &h->conv})
+                          &h->rq_cand_d, &h->rq_cand_i, &h->rq_flag, &h->hk_ws, &h->hout, &h->conv, &h->rg_qin,
+                          &h->rg_qf32, &h->rg_qop, &h->rg_eps, &h->rg_rho, &h->rg_shift, &h->rg_thr, &h->rg_cnt,
+                          &h->rg_cand, &h->rg_dist, &h->rg_sorted, &h->rg_temp, &h->rg_lims, &h->rg_D, &h->rg_I})
             b->release();
         graph_release(h);
         if (h->ghq) (void)hipHostFree(h->ghq);
@@ -1304,6 +1326,12 @@ int fx_index_set_option(FxIndex* h, const char* name, int64_t value) {
     int* slot = h->opt.find(name, value, &why);
     if (!slot) return set_err(FX_E_ARG, "unknown option '%s'", name);
     if (why) return set_err(FX_E_ARG, "option '%s': %s (%lld)", name, why, (long long)value);
+    if (slot == &h->opt.range_cap && h->rg_cand.p) {
+        // the next range search starts from the new capacity
+        DeviceGuard g(h->device);
+        HIP_TRY(hipStreamSynchronize(h->stream()));
+        h->rg_cand.release();
+    }
     *slot = (int)value;
     return FX_OK;
 }
@@ -1470,6 +1498,226 @@ int fx_index_last_exact_fallbacks(FxIndex* h, int64_t* out) {
     return FX_OK;
 }
 
+// ---- range_search (fx_range.hip) ------------------------------------------
+
+// the range scan's grid: 128-query tiles x corpus splits, sized and placed as
+// plan_scan does for the 128-row scans (>= 3 tiles per split; corpus-
+// partitioned over the XCDs once there are 8 x 3 tiles), from the shape
+// alone -- no option enters, so none can change a result
+static void plan_range_scan(const FxIndex* h, int64_t nq, ScanParams& p) {
+    p.qt = TILE_Q;
+    p.tr = TILE_R;
+    p.n_qtiles = (int)((nq + TILE_Q - 1) / TILE_Q);
+    p.n_ctiles = (int)((h->ntotal + TILE_R - 1) / TILE_R);
+    const int ntl = p.n_qtiles, nct = p.n_ctiles;
+    constexpr int min_tiles = 3;
+    p.qt_per_xcd = 0;
+    if (nct >= 8 * min_tiles) {
+        p.place = 1;
+        const int max_sx = std::max(1, nct / (8 * min_tiles));
+        int best = 1;
+        double best_eff = 0.0;
+        for (int sx = 1; sx <= std::min(max_sx, std::max(16, 128 / ntl)); ++sx) {
+            const double live = (double)ntl * sx;
+            const double eff = live / (std::ceil(live / 32.0) * 32.0);
+            if (eff > best_eff + 1e-9) { best_eff = eff; best = sx; }
+            if (eff > 0.985 && live >= 128) break;
+        }
+        p.sx = best;
+        p.splits = 8 * best;
+    } else {
+        p.place = 0;
+        p.sx = 0;
+        p.splits = fill_splits(ntl, ntl, nct, min_tiles);
+    }
+    p.grid = ntl * p.splits;
+}
+
+static int range_store_empty(FxIndex* h, int64_t nq, int64_t* lims) {
+    // no row can qualify: all-zero lims on the host and on the device
+    HIP_TRY(h->rg_lims.ensure((size_t)(nq + 1) * 8));
+    HIP_TRY(hipMemsetAsync(h->rg_lims.p, 0, (size_t)(nq + 1) * 8, h->stream()));
+    HIP_TRY(hipStreamSynchronize(h->stream()));
+    std::fill(lims, lims + nq + 1, (int64_t)0);
+    h->rg_nq = nq;
+    h->rg_total = 0;
+    return FX_OK;
+}
+
+// DevBuf growth of the range path: an allocation failure is FX_E_OOM
+#define RG_ALLOC(buf, want)                                                                          \
+    do {                                                                                             \
+        if ((buf).ensure(want) != hipSuccess) {                                                      \
+            (void)hipGetLastError();                                                                 \
+            return set_err(FX_E_OOM, "range_search: cannot allocate %zu bytes (%s)", (size_t)(want), #buf); \
+        }                                                                                            \
+    } while (0)
+
+int fx_index_range_search(FxIndex* h, int64_t nq, const void* q, int q_dtype, int q_mem, float radius,
+                          int64_t* lims) {
+    if (radius != radius) return set_err(FX_E_ARG, "range_search: radius is NaN");
+    if (!h) return set_err(FX_E_ARG, "null index");
+    if (nq < 0) return set_err(FX_E_ARG, "negative nq");
+    if (nq >= (int64_t)INT32_MAX) return set_err(FX_E_UNSUPPORTED, "range_search: more than 2^31-1 queries per call");
+    if (!check_dtype(q_dtype)) return set_err(FX_E_ARG, "bad query dtype %d", q_dtype);
+    if (!lims) return set_err(FX_E_ARG, "null lims");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    {   // the counts of a device-resident search still in flight are read first:
+        // this call reuses the dropped-ids word
+        const int rc = read_counts(h);
+        if (rc != FX_OK) return rc;
+    }
+    h->rg_nq = -1;
+    h->rg_total = 0;
+    h->rg_cands = 0;
+    h->rg_passes = 0;
+    if (nq == 0) {
+        lims[0] = 0;
+        h->rg_nq = 0;
+        return FX_OK;
+    }
+    if (!q) return set_err(FX_E_ARG, "null buffer");
+    // L2 distances are >= 0 and the test is strict: radius <= 0 takes no row
+    if (h->ntotal == 0 || (h->metric == L2 && radius <= 0.0f)) return range_store_empty(h, nq, lims);
+
+    hipStream_t s = h->stream();
+    const void* qdev = q;
+    if (q_mem == FX_MEM_HOST) {
+        const size_t qb = (size_t)nq * h->d * dtype_size(q_dtype);
+        RG_ALLOC(h->rg_qin, qb);
+        HIP_TRY(hipMemcpyAsync(h->rg_qin.p, q, qb, hipMemcpyHostToDevice, s));
+        qdev = h->rg_qin.p;
+    }
+    const int64_t nq_pad = round_up(nq, QPAD);
+    RG_ALLOC(h->rg_qf32, (size_t)nq_pad * h->kdim * 4);
+    RG_ALLOC(h->rg_qop, (size_t)nq_pad * h->row_bytes);
+    RG_ALLOC(h->rg_eps, (size_t)nq * 4);
+    RG_ALLOC(h->rg_rho, (size_t)nq * 4);
+    RG_ALLOC(h->rg_shift, (size_t)nq * 8);
+    RG_ALLOC(h->rg_thr, (size_t)nq * 4);
+    RG_ALLOC(h->rg_cnt, 8);
+    RG_ALLOC(h->rg_lims, (size_t)(nq + 1) * 8);
+    const uint64_t want_cap = h->opt.range_cap > 0 ? (uint64_t)h->opt.range_cap : (uint64_t)RANGE_CAP_DEFAULT;
+    RG_ALLOC(h->rg_cand, (size_t)want_cap * 8);
+
+    // query preparation in its no-image mode: the operand of the stored rows'
+    // dtype, uncentred, bound terms against max |y|^2
+    PrepParams pp{};
+    pp.q = qdev;
+    pp.q_dt = q_dtype;
+    pp.nq = nq;
+    pp.nq_pad = nq_pad;
+    pp.d = h->d;
+    pp.kdim = h->kdim;
+    pp.st_dt = h->dtype;
+    pp.metric = h->metric;
+    pp.qf32 = (float*)h->rg_qf32.p;
+    pp.qop = h->rg_qop.p;
+    pp.qeps = (float*)h->rg_eps.p;
+    pp.qrho = (float*)h->rg_rho.p;
+    pp.qshift = (double*)h->rg_shift.p;
+    pp.mbits = h->max_sq_bits;
+    pp.img_bits = h->max_sq_bits;
+    pp.zero[0] = h->dev_drop;
+    HIP_TRY(launch_prep_queries(pp, s));
+    HIP_TRY(launch_range_thr(nq, h->metric, radius, pp.qeps, pp.qrho, pp.qshift, (float*)h->rg_thr.p, s));
+
+    ScanParams sp{};
+    sp.codes = h->codes;
+    sp.norms = h->norms;
+    sp.ntotal = h->ntotal;
+    sp.row_bytes = h->row_bytes;
+    sp.qop = (const char*)h->rg_qop.p;
+    sp.nq = nq;
+    plan_range_scan(h, nq, sp);
+
+    // the scan; when it counted more candidates than the buffer holds, the
+    // buffer grows to the count and the scan runs once more (the count does
+    // not depend on the capacity, so the second pass fits)
+    uint64_t count = 0;
+    for (int pass = 1; pass <= 2; ++pass) {
+        const uint64_t cap = h->rg_cand.bytes / 8;
+        HIP_TRY(hipMemsetAsync(h->rg_cnt.p, 0, 8, s));
+        HIP_TRY(launch_range_scan(h->dtype, h->metric, sp, (const float*)h->rg_thr.p, (uint64_t*)h->rg_cand.p, cap,
+                                  (uint64_t*)h->rg_cnt.p, s));
+        HIP_TRY(hipMemcpyAsync(&count, h->rg_cnt.p, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        h->rg_passes = pass;
+        if (count <= cap) break;
+        if (pass == 2)
+            return set_err(FX_E_INTEGRITY, "range_search: the second scan pass counted %llu candidates for %llu slots",
+                           (unsigned long long)count, (unsigned long long)cap);
+        if (count > (uint64_t)INT32_MAX)
+            return set_err(FX_E_UNSUPPORTED, "range_search: %llu candidate pairs in one call (limit 2^31-1): "
+                           "search fewer queries per call", (unsigned long long)count);
+        RG_ALLOC(h->rg_cand, (size_t)count * 8);
+    }
+    h->rg_cands = (int64_t)count;
+    if (count == 0) return range_store_empty(h, nq, lims);
+
+    RangeFinish f{};
+    f.n = (int64_t)count;
+    HIP_TRY(range_sort_temp_bytes(f.n, nq, &f.temp_bytes));
+    RG_ALLOC(h->rg_dist, (size_t)count * 4);
+    RG_ALLOC(h->rg_sorted, (size_t)count * 8);
+    RG_ALLOC(h->rg_temp, std::max<size_t>(f.temp_bytes, 16));
+    RG_ALLOC(h->rg_D, (size_t)count * 4);
+    RG_ALLOC(h->rg_I, (size_t)count * 8);
+    f.words = (uint64_t*)h->rg_cand.p;
+    f.codes = h->codes;
+    f.row_bytes = h->row_bytes;
+    f.kdim = h->kdim;
+    f.st_dt = h->dtype;
+    f.metric = h->metric;
+    f.ntotal = h->ntotal;
+    f.qf32 = pp.qf32;
+    f.nq = nq;
+    f.radius = radius;
+    f.id_offset = h->id_offset;
+    f.dist = (float*)h->rg_dist.p;
+    f.sorted = (uint64_t*)h->rg_sorted.p;
+    f.temp = h->rg_temp.p;
+    f.n_drop = h->dev_drop;
+    f.lims = (int64_t*)h->rg_lims.p;
+    f.D = (float*)h->rg_D.p;
+    f.I = (int64_t*)h->rg_I.p;
+    HIP_TRY(launch_range_finish(f, s));
+    int dropped = 0;
+    HIP_TRY(hipMemcpyAsync(lims, f.lims, (size_t)(nq + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&dropped, h->dev_drop, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    h->last_dropped = dropped;
+    if (dropped > 0) return integrity_error(h);
+    h->rg_nq = nq;
+    h->rg_total = lims[nq];
+    return FX_OK;
+}
+#undef RG_ALLOC
+
+int fx_index_range_result(FxIndex* h, float* D, int64_t* I, int out_mem) {
+    if (!h) return set_err(FX_E_ARG, "null index");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->rg_nq < 0) return set_err(FX_E_ARG, "range_result: no range search result is stored");
+    if (h->rg_total == 0) return FX_OK;
+    if (!D || !I) return set_err(FX_E_ARG, "null buffer");
+    DeviceGuard g(h->device);
+    hipStream_t s = h->stream();
+    const hipMemcpyKind kind = out_mem == FX_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    HIP_TRY(hipMemcpyAsync(D, h->rg_D.p, (size_t)h->rg_total * 4, kind, s));
+    HIP_TRY(hipMemcpyAsync(I, h->rg_I.p, (size_t)h->rg_total * 8, kind, s));
+    if (out_mem == FX_MEM_HOST) HIP_TRY(hipStreamSynchronize(s));
+    return FX_OK;
+}
+
+int fx_index_last_range_stats(FxIndex* h, int64_t* candidates, int* passes) {
+    if (!h || !candidates || !passes) return set_err(FX_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    *candidates = h->rg_cands;
+    *passes = h->rg_passes;
+    return FX_OK;
+}
+
 int fx_index_reset(FxIndex* h) {
     if (!h) return set_err(FX_E_ARG, "null index");
     std::lock_guard<std::mutex> lk(h->mu);
@@ -1483,6 +1731,8 @@ int fx_index_reset(FxIndex* h) {
     h->ntotal = 0;
     h->img_rows = 0;
     h->mu_rows = 0;
+    h->rg_nq = -1;  // the last range search's result goes with the rows
+    h->rg_total = 0;
     return FX_OK;
 }
 

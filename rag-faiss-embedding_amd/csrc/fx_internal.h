@@ -233,6 +233,39 @@ hipError_t launch_hugek_search(const HugeKParams& p, void* ws, size_t ws_bytes, 
 constexpr int FX_HUGEK_MAX_SHARDS = 64;
 hipError_t launch_merge_shards_sort(int metric, int nshards, int64_t nq, int k, const float* D_in,
                                     const int64_t* I_in, float* D_out, int64_t* I_out, hipStream_t s);
+// range_search (fx_range.hip).  thr[q] = T_q, the largest scan key a row
+// within `radius` of query q can have (from k_prep_queries' E, rho, s_q).
+hipError_t launch_range_thr(int64_t nq, int metric, float radius, const float* qeps, const float* qrho,
+                            const double* qshift, float* thr, hipStream_t s);
+// the MFMA filter over the stored rows (p.codes / p.norms = the index's own,
+// p.qt = TILE_Q, p.tr = TILE_R, placement fields as map_block reads them):
+// every (query, row) pair with key <= thr[query] -> cand[] as query << 32 | row
+// at positions reserved from *counter, which counts past `cap` (entries at
+// or past cap are not stored).  *counter must be 0 before the launch.
+hipError_t launch_range_scan(int st_dt, int metric, const ScanParams& p, const float* thr, uint64_t* cand,
+                             uint64_t cap, uint64_t* counter, hipStream_t s);
+// exact verification, compaction and unpacking of n candidate words
+struct RangeFinish {
+    uint64_t* words;       // [n] candidates (overwritten: failing ones -> all ones)
+    int64_t n;             // 1 .. INT_MAX
+    const char* codes;     // stored rows (storage dtype st_dt)
+    int row_bytes, kdim, st_dt, metric;
+    int64_t ntotal;
+    const float* qf32;     // [nq][kdim] fp32 queries, zero padded
+    int64_t nq;
+    float radius;
+    int64_t id_offset;
+    float* dist;           // [n] scratch: exact distance of words[i]
+    uint64_t* sorted;      // [n] scratch: words in (query, row) order, sentinels last
+    void* temp;            // rocPRIM temporaries (range_sort_temp_bytes)
+    size_t temp_bytes;
+    int* n_drop;           // words naming a query / row outside the index are counted here, never gathered
+    int64_t* lims;         // out [nq + 1]
+    float* D;              // out [n]: the first lims[nq] are the results
+    int64_t* I;            // out [n]
+};
+hipError_t range_sort_temp_bytes(int64_t n, int64_t nq, size_t* bytes);
+hipError_t launch_range_finish(const RangeFinish& f, hipStream_t s);
 // fp32 code rows [r0, r1) -> their F32S scan image (same row stride)
 // (centred by mu when non-null), with the image rows' |v|^2 -> cnorms and their
 // maximum -> cmax_bits (atomicMax)

@@ -552,33 +552,7 @@ __global__ __launch_bounds__(256) void k_prep_queries(PrepParams p, double gamma
 // ---------------------------------------------------------------------------
 // the fused scan kernel
 // ---------------------------------------------------------------------------
-template <int DT> struct Frag;
-template <> struct Frag<BF16> {
-    typedef bf16x8 T;
-    static __device__ __forceinline__ f32x4 mma(T a, T b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Frag<F16> {
-    typedef f16x8 T;
-    static __device__ __forceinline__ f32x4 mma(T a, T b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Frag<F32> {
-    typedef f32x4 T;
-    // one 1-KiB fragment block holds 16 rows x 16 k: lane l has row l&15,
-    // k = 4(l>>4) .. 4(l>>4)+3.  MFMA step j sums k = 4c+j (c = l>>4): every
-    // k is covered exactly once; A and B use the same permutation.
-    static __device__ __forceinline__ f32x4 mma(T a, T b, f32x4 c) {
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
-        return c;
-    }
-};
-
+// (Frag<DT>, the builtin-MFMA fragment types: fx_device.h, shared with fx_range.hip)
 template <int DT, int METRIC>
 __global__ __launch_bounds__(SCAN_THREADS, 1) void k_scan_topk(ScanParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];

@@ -7,7 +7,8 @@ as faiss``:
 
 * ``IndexFlatL2(d)`` / ``IndexFlatIP(d)`` with ``.d``, ``.ntotal``,
   ``.metric_type``, ``.is_trained``, ``.add(x)``, ``.search(x, k) -> (D, I)``,
-  ``.reset()``, ``.reconstruct_n(i0, n)``;
+  ``.range_search(x, radius) -> (lims, D, I)``, ``.reset()``,
+  ``.reconstruct_n(i0, n)``;
 * ``write_index(index, path)`` / ``read_index(path)`` on the IxF2 format.
 
 Inputs may be numpy arrays (as in the reference: host fp32, results returned
@@ -165,6 +166,51 @@ class _FlatIndex:
         self._check(self._lib.fx_index_search(self._h, nq, x.ctypes.data, _lib.F32, _lib.MEM_HOST, k,
                                               Dh.ctypes.data, Ih.ctypes.data, _lib.MEM_HOST))
         return Dh, Ih
+
+    def range_search(self, x, radius: float) -> Tuple:
+        """``IndexFlat.range_search``: every row within ``radius`` of each
+        query row -- ``D < radius`` (L2 index) or ``x.y > radius`` (IP), both
+        strict, decided on the exact distance.  Returns ``(lims, D, I)``:
+        query i owns ``D[lims[i]:lims[i+1]]`` / ``I[lims[i]:lims[i+1]]``,
+        ordered by ascending row id.  numpy in -> numpy out (``lims`` uint64,
+        as faiss); a device tensor in -> D and I device tensors and ``lims``
+        an int64 tensor on the same device."""
+        radius = float(radius)
+        dev_in = _is_device_tensor(x)
+        if dev_in:
+            t = _torch()
+            assert x.dim() == 2 and x.shape[1] == self.d, "dimension mismatch"
+            assert x.device.index == self.device, f"queries on cuda:{x.device.index}, index on cuda:{self.device}"
+            x = x.contiguous()
+            nq, qptr, qdt, mem = x.shape[0], ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x), _lib.MEM_DEVICE
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+            assert x.ndim == 2 and x.shape[1] == self.d, "dimension mismatch"
+            nq, qptr, qdt, mem = x.shape[0], ctypes.c_void_p(x.ctypes.data), _lib.F32, _lib.MEM_HOST
+        lims = np.zeros(nq + 1, dtype=np.int64)
+        self._bind_stream(dev_in)
+        self._check(self._lib.fx_index_range_search(self._h, nq, qptr, qdt, mem, radius,
+                                                    lims.ctypes.data_as(ctypes.c_void_p)))
+        total = int(lims[nq])
+        if dev_in:
+            D = t.empty((total,), dtype=t.float32, device=x.device)
+            I = t.empty((total,), dtype=t.int64, device=x.device)
+            self._check(self._lib.fx_index_range_result(self._h, ctypes.c_void_p(D.data_ptr()),
+                                                        ctypes.c_void_p(I.data_ptr()), _lib.MEM_DEVICE))
+            return t.from_numpy(lims).to(x.device), D, I
+        D = np.empty(total, dtype=np.float32)
+        I = np.empty(total, dtype=np.int64)
+        self._check(self._lib.fx_index_range_result(self._h, D.ctypes.data_as(ctypes.c_void_p),
+                                                    I.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST))
+        return lims.astype(np.uint64), D, I
+
+    def last_range_stats(self) -> dict:
+        """Of the last ``range_search``: ``candidates`` the MFMA scan emitted
+        (the exact pass kept the result's share of them) and scan ``passes``
+        run (2 when the candidate buffer had to grow; 0: no scan needed)."""
+        c, p = ctypes.c_int64(0), ctypes.c_int(0)
+        self._check(self._lib.fx_index_last_range_stats(self._h, ctypes.byref(c), ctypes.byref(p)))
+        return {"candidates": c.value, "passes": p.value}
 
     def last_fallbacks(self) -> int:
         """Queries of the last search whose top-k the scan's candidates could

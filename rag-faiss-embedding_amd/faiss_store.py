@@ -85,6 +85,30 @@ class FAISSVectorStore:
             logger.error("search failed: %s", e)
             return np.array([]), []
 
+    def search_radius(self, query_vector, radius: float) -> Tuple[np.ndarray, List[int]]:
+        """Every stored vector within squared L2 distance ``radius`` of one
+        query (``index.range_search``; strict, exact membership) -- the
+        thresholded form of ``search``: "every chunk with score >= s" is
+        ``radius = 1/s - 1`` under the front ends' ``1 / (1 + d)``.  Rows map
+        to document ids with ``search``'s filter (rows past the id list are
+        dropped); results are sorted by (distance, row).  On any error the
+        result is ``(np.array([]), [])``, as ``search``."""
+        try:
+            q = query_vector
+            if isinstance(q, list):
+                q = np.array(q, dtype=np.float32)
+            _, dist, rows = self.index.range_search(q.reshape(1, -1), float(radius))
+            if not isinstance(dist, np.ndarray):  # device tensors -> host
+                dist, rows = dist.cpu().numpy(), rows.cpu().numpy()
+            n_ids = len(self.doc_ids)
+            keep = sorted((float(dv), int(r)) for dv, r in zip(dist, rows) if 0 <= r < n_ids)
+            found = [self.doc_ids[r] for _, r in keep]
+            logger.info("search_radius %g over %d rows -> %d hits", radius, self.index.ntotal, len(found))
+            return np.array([dv for dv, _ in keep], dtype=np.float32) if keep else np.array([]), found
+        except Exception as e:  # noqa: BLE001 -- same contract as search
+            logger.error("search_radius failed: %s", e)
+            return np.array([]), []
+
     def save_index(self, filepath: Optional[str] = None):
         """faiss_store.py:83-97: IxF2 index file + pickle-protocol-4 id list
         at ``<path>.mapping``."""

@@ -144,6 +144,60 @@ def query_engine_search(store_index, store: DocumentStore, query_embeddings, top
         return [[] for _ in range(n)]
 
 
+def radius_for_score(min_score: float) -> float:
+    """The L2 radius of ``score >= min_score`` under ``similarity``:
+    1 / (1 + d) >= s  <=>  d <= 1/s - 1, for 0 < s <= 1."""
+    s = float(min_score)
+    if not 0.0 < s <= 1.0:
+        raise ValueError(f"min_score must be in (0, 1] (got {min_score})")
+    return 1.0 / s - 1.0
+
+
+def documents_within(index, doc_ids: Sequence[int], store: DocumentStore, query_embeddings, *,
+                     max_distance: Optional[float] = None, min_score: Optional[float] = None) -> List[List[Dict]]:
+    """Every document within a threshold of each query row, nearest first
+    (ties: smaller index row) -- "every chunk with score >= 0.6" instead of
+    "the best 5, however bad".  Exactly one of ``max_distance`` (the index's
+    radius: squared L2 distance, strict) and ``min_score`` (the front ends'
+    ``1 / (1 + d)``, L2 indexes only; radius ``1/s - 1``) is given.  One
+    ``index.range_search`` and one ``fetch_many`` per batch; each document
+    carries ``distance`` and ``score``.  Errors are logged and give empty
+    lists, as the other callers here."""
+    try:
+        if (max_distance is None) == (min_score is None):
+            raise ValueError("give exactly one of max_distance and min_score")
+        if min_score is not None:
+            if getattr(index, "metric_type", 1) != 1:
+                raise ValueError("min_score needs an L2 index")
+            radius = radius_for_score(min_score)
+        else:
+            radius = float(max_distance)
+        lims, D, I = index.range_search(query_embeddings, radius)
+        lims, D, I = _to_numpy(lims).astype(np.int64), _to_numpy(D), _to_numpy(I)
+        ids = np.asarray(doc_ids, dtype=np.int64)
+        valid = (I >= 0) & (I < len(ids))
+        docs = store.fetch_many(ids[I[valid]].tolist())
+        results: List[List[Dict]] = []
+        for qi in range(len(lims) - 1):
+            lo, hi = int(lims[qi]), int(lims[qi + 1])
+            row: List[Dict] = []
+            for dist, idx in sorted(zip(D[lo:hi].tolist(), I[lo:hi].tolist())):
+                if idx < 0 or idx >= len(ids):
+                    continue
+                doc = docs.get(int(ids[idx]))
+                if doc is not None:
+                    d = dict(doc)
+                    d["distance"] = float(dist)
+                    d["score"] = similarity(float(dist))
+                    row.append(d)
+            results.append(row)
+        return results
+    except Exception as e:  # noqa: BLE001 -- same contract as search_similar_documents
+        logger.error("Error searching documents within a radius: %s", e)
+        n = getattr(query_embeddings, "shape", [1])[0] if hasattr(query_embeddings, "shape") else 1
+        return [[] for _ in range(n)]
+
+
 class RetrievalEngine:
     """Encoder + index + document store: the retrieval half of the
     reference's CLI / QueryEngine, batched.  ``search(texts, k)`` encodes all
@@ -164,6 +218,15 @@ class RetrievalEngine:
         if not texts:
             return []
         return search_similar_documents(self.index, self.doc_ids, self.store, self.embed(texts), k)
+
+    def search_within(self, texts: List[str], *, max_distance: Optional[float] = None,
+                      min_score: Optional[float] = None) -> List[List[Dict]]:
+        """Every document within ``max_distance`` (or scoring at least
+        ``min_score``) of each text: ``documents_within`` over one encoder pass."""
+        if not texts:
+            return []
+        return documents_within(self.index, self.doc_ids, self.store, self.embed(texts),
+                                max_distance=max_distance, min_score=min_score)
 
     def search_one(self, text: str, k: int = 5) -> List[Dict]:
         """The reference's single-query call shape (rag_datastore_manager.py:211)."""

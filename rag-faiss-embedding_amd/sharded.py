@@ -33,6 +33,11 @@ class ShardedIndexFlatL2:
     add(x_global_block, row0): every rank is handed a block of global rows
     starting at ``row0`` (the same block on every rank, or only its own part)
     and keeps the rows it owns; ``n_total`` fixes the ownership split.
+
+    ``range_search`` is not offered here: its variable-length per-rank
+    results need a different exchange than the fixed (nq x k) all_gather.
+    A caller that wants it runs ``local.range_search`` per rank (ids are
+    global through the id offset) and concatenates.
     """
 
     def __init__(self, d: int, n_total: int, dtype: str = "float32", group=None, device: Optional[int] = None,
