@@ -1,6 +1,8 @@
 // fx_device.h -- device-side helpers shared by the HIP translation units
-// (fx_kernels.hip: add/refine/merge/synth + generic scan; fx_scan.hip: the
-// MFMA scan).  Header-only, all inline.
+// (fx_kernels.hip, fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip):
+// conversions, the exact fp64 distance, wave sorts and sums, block placement,
+// the block top-K, the plain scans' tile loop (scan_tiles_128) and the MFMA
+// wrappers of k_scan_v4 / k_scan_v5.  Header-only, all inline.
 #pragma once
 #include "fx_internal.h"
 
@@ -424,6 +426,120 @@ template <> struct Frag<F32> {
         return c;
     }
 };
+
+// ---------------------------------------------------------------------------
+// The 128-row x 128-query tile loop of the plain scans (k_scan_topk,
+// k_range_scan): 4 waves as 2 x 2, each a 64 x 64 block of the tile as 4 x 4
+// MFMA accumulators; rows and queries staged STAGE_B bytes at a time through
+// an LDS-DMA double buffer at smem[0, LDS_STAGE), the tiles' row norms through
+// two 512-B slots at LDS_NORM_OFF.
+// ---------------------------------------------------------------------------
+// accumulator (m, n, i) of a lane <-> (corpus row, query column of the tile)
+__device__ __forceinline__ int tile_qloc(int n) {
+    return ((threadIdx.x >> 6) & 1) * 64 + n * 16 + (threadIdx.x & 15);
+}
+// local row of (m, i) in the tile, given the lane's local row rl0 of
+// (m = 0, i = 0): the row exists when it is < rlim, and is row
+// trow0 + tile_rloc of the index
+__device__ __forceinline__ int tile_rloc(int rl0, int m, int i) { return rl0 + m * 16 + i; }
+
+// Scans the corpus tiles of `split` against query tile `qtile` and calls
+// ep(acc, yn, trow0, rlim, rl0) once per finished tile, uniformly by all 256
+// threads (ep may hold block barriers).  The key of (m, n, i) is
+// acc[m][n][i] + yn[m][i] for L2 and acc[m][n][i] for IP: an IP scan never
+// reads the row norms, so their DMA is not issued and yn is 0.  What the
+// caller wrote to LDS before the call is visible to every thread inside ep.
+template <int DT, int METRIC, class Epilogue>
+__device__ __forceinline__ void scan_tiles_128(const ScanParams& p, char* smem, int qtile, int split, Epilogue&& ep) {
+    typedef typename Frag<DT>::T frag_t;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int ct0 = (int)((int64_t)split * p.n_ctiles / p.splits);
+    const int ct1 = (int)((int64_t)(split + 1) * p.n_ctiles / p.splits);
+    const int nks = p.row_bytes / STAGE_B;
+    const int G = (ct1 - ct0) * nks;
+    const int rb = p.row_bytes;
+
+    // per-lane byte offsets of this wave's 4 A blocks and 4 B blocks inside a
+    // tile (fragment-ordered image: block bi = 16-row block * 2 + 64-B half)
+    int offs[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int bi = wave * 4 + j, rblk = bi >> 1, kb = bi & 1;
+        offs[j] = (rblk * 16 + (lane & 15)) * rb + kb * 64 + (lane >> 4) * 16;
+    }
+    const char* qbase = p.qop + (int64_t)qtile * TILE_Q * rb;
+
+    auto issue = [&](int g) {
+        const int t = g / nks, ks = g - t * nks;
+        char* buf = smem + (g & 1) * ((TILE_R + TILE_Q) * STAGE_B);
+        const int64_t row0 = (int64_t)(ct0 + t) * TILE_R;
+        const char* abase = p.codes + row0 * rb + ks * STAGE_B;
+        const char* bbase = qbase + ks * STAGE_B;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            glds16(abase + offs[j], buf + (wave * 4 + j) * 1024);
+            glds16(bbase + offs[j], buf + TILE_R * STAGE_B + (wave * 4 + j) * 1024);
+        }
+        if (METRIC == L2 && ks == 0 && wave == 0 && lane < 32)
+            glds16(p.norms + row0 + lane * 4, smem + LDS_NORM_OFF + (t & 1) * (TILE_R * 4));
+    };
+
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    if (G > 0) issue(0);
+    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+
+    int t = 0, ks = 0;
+    for (int g = 0; g < G; ++g) {
+        if (g + 1 < G) issue(g + 1);
+        const char* buf = smem + (g & 1) * ((TILE_R + TILE_Q) * STAGE_B);
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            frag_t a[4], b[4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) a[m] = *(const frag_t*)(buf + ((wm * 4 + m) * 2 + kb) * 1024 + lane * 16);
+#pragma unroll
+            for (int n = 0; n < 4; ++n)
+                b[n] = *(const frag_t*)(buf + TILE_R * STAGE_B + ((wn * 4 + n) * 2 + kb) * 1024 + lane * 16);
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int n = 0; n < 4; ++n) acc[m][n] = Frag<DT>::mma(a[m], b[n], acc[m][n]);
+        }
+
+        if (__builtin_expect(ks == nks - 1, 0)) {  // (the stage loop is the straight path)
+            const float* nb = (const float*)(smem + LDS_NORM_OFF + (t & 1) * (TILE_R * 4));
+            const int trow0 = (ct0 + t) * TILE_R;
+            const int rlim = (int)(p.ntotal - (int64_t)trow0);  // rows of this tile that exist
+            const int rl0 = wm * 64 + 4 * (lane >> 4);           // local row of (m = 0, i = 0)
+            float yn[4][4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                if (METRIC == L2) {
+                    float4 v = *(const float4*)(nb + rl0 + m * 16);
+                    yn[m][0] = v.x; yn[m][1] = v.y; yn[m][2] = v.z; yn[m][3] = v.w;
+                } else {
+                    yn[m][0] = yn[m][1] = yn[m][2] = yn[m][3] = 0.f;
+                }
+            }
+            ep(acc, yn, trow0, rlim, rl0);
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+            ks = 0;
+            ++t;
+        } else {
+            ++ks;
+        }
+        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+    }
+}
 
 // f32: a 64-B k-chunk is 4 k-steps of 16x16x4 (see Frag<F32>); B is kept as 4
 // scalar AGPRs per chunk.

@@ -164,23 +164,13 @@ hipError_t carve(int64_t ntotal, int kdim, int qb, HkCarve* c) {
     return hipSuccess;
 }
 
-template <int DT, int METRIC>
-void launch_keys_t(const HugeKParams& p, const float* qf32, int qb, int idbits, uint64_t* keys, hipStream_t s) {
+hipError_t launch_keys(const HugeKParams& p, const float* qf32, int qb, int idbits, uint64_t* keys, hipStream_t s) {
     const int64_t items = p.ntotal * ((qb + HK_QB - 1) / HK_QB);
-    hipLaunchKernelGGL((k_hk_keys<DT, METRIC>), dim3(grid_for(items)), dim3(HK_THREADS), 0, s, p.codes, p.row_bytes,
-                       p.kdim, p.ntotal, qf32, qb, idbits, keys);
-}
-
-void launch_keys(const HugeKParams& p, const float* qf32, int qb, int idbits, uint64_t* keys, hipStream_t s) {
-    if (p.metric == L2) {
-        if (p.st_dt == F32) launch_keys_t<F32, L2>(p, qf32, qb, idbits, keys, s);
-        else if (p.st_dt == BF16) launch_keys_t<BF16, L2>(p, qf32, qb, idbits, keys, s);
-        else launch_keys_t<F16, L2>(p, qf32, qb, idbits, keys, s);
-    } else {
-        if (p.st_dt == F32) launch_keys_t<F32, IP>(p, qf32, qb, idbits, keys, s);
-        else if (p.st_dt == BF16) launch_keys_t<BF16, IP>(p, qf32, qb, idbits, keys, s);
-        else launch_keys_t<F16, IP>(p, qf32, qb, idbits, keys, s);
-    }
+    return dispatch_dt_metric<DT_STORED>(p.st_dt, p.metric, [&](auto dt, auto mt) {
+        hipLaunchKernelGGL((k_hk_keys<dt(), mt()>), dim3(grid_for(items)), dim3(HK_THREADS), 0, s, p.codes,
+                           p.row_bytes, p.kdim, p.ntotal, qf32, qb, idbits, keys);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace
@@ -216,8 +206,7 @@ hipError_t launch_hugek_search(const HugeKParams& p, void* ws, size_t ws_bytes, 
         const int nb = (int)std::min<int64_t>(qb, p.nq - b0);
         hipLaunchKernelGGL(k_hk_queries, dim3(grid_for((int64_t)nb * p.kdim)), dim3(HK_THREADS), 0, s,
                            (const char*)p.q + b0 * p.d * esz, p.q_dt, (int64_t)nb, p.d, p.kdim, qf32);
-        launch_keys(p, qf32, nb, idbits, keys, s);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = launch_keys(p, qf32, nb, idbits, keys, s)) != hipSuccess) return e;
         size_t tb = c.temp_bytes;
         if (p.ntotal > HK_SEG_SORT_MAX) {
             for (int j = 0; j < nb; ++j) {

@@ -406,6 +406,45 @@ int fill_splits(int live_tiles, int eff_tiles, int n_ctiles, int min_tiles) {
     return best;
 }
 
+// The shape-only part of a scan's grid (map_tile's fields), for ntl query
+// tiles and nct corpus tiles with >= min_tiles tiles per split.  partition:
+// corpus-partitioned placement is admissible (taken once every XCD gets
+// min_tiles tiles); group_qtiles: placement 0 gives each XCD a fixed group of
+// query tiles when there are >= 8.  No index and no option enters.
+struct SplitPlan {
+    int place, sx, splits, qt_per_xcd;
+    int qslots;  // workgroups per split: ntl, or 8 qt_per_xcd
+    void store(ScanParams& p) const {
+        p.place = place;
+        p.sx = sx;
+        p.splits = splits;
+        p.qt_per_xcd = qt_per_xcd;
+        p.grid = qslots * splits;
+    }
+};
+SplitPlan plan_splits(int ntl, int nct, int min_tiles, bool partition, bool group_qtiles) {
+    SplitPlan s = {0, 0, 1, 0, ntl};
+    if (partition && nct >= 8 * min_tiles) {
+        // XCD x owns 1/8 of the corpus for every query tile; sx splits per
+        // XCD so that its ntl * sx blocks fill whole rounds of its 32 CUs
+        s.place = 1;
+        const int max_sx = std::max(1, nct / (8 * min_tiles));
+        double best_eff = 0.0;
+        for (int sx = 1; sx <= std::min(max_sx, std::max(16, 128 / ntl)); ++sx) {
+            const double live = (double)ntl * sx;
+            const double eff = live / (std::ceil(live / 32.0) * 32.0);
+            if (eff > best_eff + 1e-9) { best_eff = eff; s.sx = sx; }
+            if (eff > 0.985 && live >= 128) break;
+        }
+        s.splits = 8 * s.sx;
+    } else {
+        s.qt_per_xcd = group_qtiles && ntl >= 8 ? (ntl + 7) / 8 : 0;
+        if (s.qt_per_xcd > 0) s.qslots = 8 * s.qt_per_xcd;
+        s.splits = fill_splits(ntl, s.qslots, nct, min_tiles);
+    }
+    return s;
+}
+
 // the scan's grid: corpus splits per query tile and block placement.
 // k > KP: no cross-split pruning (ScanParams.share = 0) and at least k/4
 // splits, so that a split's KP-list rarely holds fewer than all of its top-k
@@ -426,8 +465,6 @@ void plan_scan(const FxIndex* h, int64_t nq, int k, ScanParams& p) {
     p.tr = v5 ? V5_TR : TILE_R;
     p.n_qtiles = (int)((nq + p.qt - 1) / p.qt);
     p.n_ctiles = (int)((h->ntotal + p.tr - 1) / p.tr);
-    p.place = 0;
-    p.sx = 0;
     p.pub = nullptr;
     p.prune_rank = KP;
     // default 48: with the union bound deferred a compaction is cheap enough
@@ -452,32 +489,16 @@ void plan_scan(const FxIndex* h, int64_t nq, int k, ScanParams& p) {
     // split is fetched past L2 once for all of them (nq = 256: once instead
     // of twice)
     const int place = h->opt.place >= 0 ? h->opt.place : 1;
-    if (place == 1 && nct >= 8 * min_tiles) {
-        // XCD x owns 1/8 of the corpus for every query tile; sx splits per
-        // XCD so that its ntl * sx blocks fill whole rounds of its 32 CUs
-        p.place = 1;
-        p.qt_per_xcd = 0;
+    SplitPlan sp = plan_splits(ntl, nct, min_tiles, place == 1, true);
+    if (sp.place == 1) {
         const int max_sx = std::max(1, nct / (8 * min_tiles));
-        int best = 1;
-        double best_eff = 0.0;
-        for (int sx = 1; sx <= std::min(max_sx, std::max(16, 128 / ntl)); ++sx) {
-            const double live = (double)ntl * sx;
-            const double eff = live / (std::ceil(live / 32.0) * 32.0);
-            if (eff > best_eff + 1e-9) { best_eff = eff; best = sx; }
-            if (eff > 0.985 && live >= 128) break;
-        }
-        if (h->opt.sx > 0) best = std::max(1, std::min(max_sx, h->opt.sx));  // placement A/B runs only
-        if (k > KP) best = std::max(best, std::min(max_sx, ((k + 3) / 4 + 7) / 8));
-        p.sx = best;
-        p.splits = 8 * best;
-        p.grid = 8 * ntl * best;
-    } else {
-        p.qt_per_xcd = ntl >= 8 ? (ntl + 7) / 8 : 0;
-        const int eff_q = p.qt_per_xcd > 0 ? 8 * p.qt_per_xcd : ntl;
-        p.splits = fill_splits(ntl, eff_q, nct, min_tiles);
-        if (k > KP) p.splits = std::max(p.splits, std::min(std::max(1, nct / min_tiles), (k + 3) / 4));
-        p.grid = eff_q * p.splits;
+        if (h->opt.sx > 0) sp.sx = std::max(1, std::min(max_sx, h->opt.sx));  // placement A/B runs only
+        if (k > KP) sp.sx = std::max(sp.sx, std::min(max_sx, ((k + 3) / 4 + 7) / 8));
+        sp.splits = 8 * sp.sx;
+    } else if (k > KP) {
+        sp.splits = std::max(sp.splits, std::min(std::max(1, nct / min_tiles), (k + 3) / 4));
     }
+    sp.store(p);
     // union-bound window (compact_regs): as many splits as there are, up to
     // 64, each contributing its first 256 / window published keys
     const int uw = h->opt.union_w;
@@ -1500,8 +1521,8 @@ int fx_index_last_exact_fallbacks(FxIndex* h, int64_t* out) {
 
 // ---- range_search (fx_range.hip) ------------------------------------------
 
-// the range scan's grid: 128-query tiles x corpus splits, sized and placed as
-// plan_scan does for the 128-row scans (>= 3 tiles per split; corpus-
+// the range scan's grid: 128-query tiles x corpus splits, sized and placed by
+// plan_splits as plan_scan's 128-row scans are (>= 3 tiles per split; corpus-
 // partitioned over the XCDs once there are 8 x 3 tiles), from the shape
 // alone -- no option enters, so none can change a result
 static void plan_range_scan(const FxIndex* h, int64_t nq, ScanParams& p) {
@@ -1509,28 +1530,7 @@ static void plan_range_scan(const FxIndex* h, int64_t nq, ScanParams& p) {
     p.tr = TILE_R;
     p.n_qtiles = (int)((nq + TILE_Q - 1) / TILE_Q);
     p.n_ctiles = (int)((h->ntotal + TILE_R - 1) / TILE_R);
-    const int ntl = p.n_qtiles, nct = p.n_ctiles;
-    constexpr int min_tiles = 3;
-    p.qt_per_xcd = 0;
-    if (nct >= 8 * min_tiles) {
-        p.place = 1;
-        const int max_sx = std::max(1, nct / (8 * min_tiles));
-        int best = 1;
-        double best_eff = 0.0;
-        for (int sx = 1; sx <= std::min(max_sx, std::max(16, 128 / ntl)); ++sx) {
-            const double live = (double)ntl * sx;
-            const double eff = live / (std::ceil(live / 32.0) * 32.0);
-            if (eff > best_eff + 1e-9) { best_eff = eff; best = sx; }
-            if (eff > 0.985 && live >= 128) break;
-        }
-        p.sx = best;
-        p.splits = 8 * best;
-    } else {
-        p.place = 0;
-        p.sx = 0;
-        p.splits = fill_splits(ntl, ntl, nct, min_tiles);
-    }
-    p.grid = ntl * p.splits;
+    plan_splits(p.n_qtiles, p.n_ctiles, 3, true, false).store(p);
 }
 
 static int range_store_empty(FxIndex* h, int64_t nq, int64_t* lims) {

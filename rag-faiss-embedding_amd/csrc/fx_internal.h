@@ -1,8 +1,13 @@
-// fx_internal.h -- shared between the HIP kernels (fx_kernels.hip) and the
-// host C ABI (fx_index.cpp).  Not part of the public ABI (include/fx_index.h).
+// fx_internal.h -- shared between the HIP translation units (fx_kernels.hip,
+// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip) and the host C ABI
+// (fx_index.cpp): tiling constants, kernel parameter blocks, the launchers'
+// prototypes and their host-side helpers.  Not part of the public ABI
+// (include/fx_index.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 namespace fx {
 
@@ -159,6 +164,55 @@ hipError_t launch_rescan_chunks(const int* n_flag, int cap, int nchunks, int* co
 // graph_build): the scan launchers then skip hipFuncSetAttribute, which the
 // do_search right before the capture has already applied for the same kernel.
 extern thread_local bool g_graph_capture;
+
+// Launch of a kernel with more than 64 KiB of dynamic LDS: the opt-in (per
+// device; cheap to repeat; skipped while capturing, see above), the launch,
+// its error.
+template <class... P, class... A>
+hipError_t launch_with_lds(void (*kernel)(P...), int grid, int block, int lds_bytes, hipStream_t s, const A&... args) {
+    if (!g_graph_capture) {
+        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_bytes, s, args...);
+    return hipGetLastError();
+}
+
+// (dtype, metric) as compile-time constants: f(integral_constant<int, DT>,
+// integral_constant<int, METRIC>) -> hipError_t for the run-time pair, with f
+// instantiated for the dtypes of ALLOWED only.  A dtype outside ALLOWED is
+// hipErrorInvalidValue (every caller has validated it by then: the storage
+// dtype at fx_index_create, the scan dtype by image_kind); a metric other than
+// L2 is IP.
+constexpr unsigned DT_16BIT = 1u << BF16 | 1u << F16;  // k_scan_v5, the centred norms
+constexpr unsigned DT_STORED = DT_16BIT | 1u << F32;   // what an index stores
+constexpr unsigned DT_SCAN = DT_STORED | 1u << F32S;   // ... and what k_scan_v4 also reads
+template <unsigned ALLOWED, int DT, int METRIC, class F>
+hipError_t dispatch_one(F&& f) {
+    if constexpr ((ALLOWED >> DT & 1u) != 0)
+        return f(std::integral_constant<int, DT>{}, std::integral_constant<int, METRIC>{});
+    else
+        return hipErrorInvalidValue;
+}
+template <unsigned ALLOWED, class F>
+hipError_t dispatch_dt_metric(int dt, int metric, F&& f) {
+    // The order of these branches is the order in which f is instantiated, and so
+    // the order in which a translation unit's kernels are emitted: F32S first, then
+    // metric-major.  Keep it: comparing the device assembly of fx_scan.hip and
+    // fx_scan5.hip with an earlier commit's (the check that a change did not
+    // reach the hot kernels) relies on the kernels keeping their places.
+    if (dt == F32S) return metric == L2 ? dispatch_one<ALLOWED, F32S, L2>(f) : dispatch_one<ALLOWED, F32S, IP>(f);
+    if (metric == L2) {
+        if (dt == F32) return dispatch_one<ALLOWED, F32, L2>(f);
+        if (dt == BF16) return dispatch_one<ALLOWED, BF16, L2>(f);
+        if (dt == F16) return dispatch_one<ALLOWED, F16, L2>(f);
+    } else {
+        if (dt == F32) return dispatch_one<ALLOWED, F32, IP>(f);
+        if (dt == BF16) return dispatch_one<ALLOWED, BF16, IP>(f);
+        if (dt == F16) return dispatch_one<ALLOWED, F16, IP>(f);
+    }
+    return hipErrorInvalidValue;
+}
 
 // launchers (stream-ordered, no host sync) -- fx_kernels.hip
 hipError_t launch_convert_rows(const void* x, int x_dt, int64_t n, int d, void* codes_row0, int st_dt,

@@ -552,24 +552,18 @@ __global__ __launch_bounds__(256) void k_prep_queries(PrepParams p, double gamma
 // ---------------------------------------------------------------------------
 // the fused scan kernel
 // ---------------------------------------------------------------------------
-// (Frag<DT>, the builtin-MFMA fragment types: fx_device.h, shared with fx_range.hip)
+// (the tile loop scan_tiles_128: fx_device.h, shared with fx_range.hip; here
+// its epilogue, the LDS candidate lists and the final flush)
 template <int DT, int METRIC>
 __global__ __launch_bounds__(SCAN_THREADS, 1) void k_scan_topk(ScanParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef typename Frag<DT>::T frag_t;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
     int qtile, split;
     map_block(blockIdx.x, p, qtile, split);
     const int64_t nq = p.nq_dev ? min((int64_t)*p.nq_dev, p.nq) : p.nq;
     if (qtile >= p.n_qtiles || (int64_t)qtile * TILE_Q >= nq) return;
-    const int ct0 = (int)((int64_t)split * p.n_ctiles / p.splits);
-    const int ct1 = (int)((int64_t)(split + 1) * p.n_ctiles / p.splits);
-    const int nks = p.row_bytes / STAGE_B;
-    const int G = (ct1 - ct0) * nks;
     const int64_t q0 = (int64_t)qtile * TILE_Q;
-    const int rb = p.row_bytes;
 
     float* lst_d = (float*)(smem + LDS_LD_OFF);
     int* lst_i = (int*)(smem + LDS_LI_OFF);
@@ -580,148 +574,77 @@ __global__ __launch_bounds__(SCAN_THREADS, 1) void k_scan_topk(ScanParams p) {
     for (int x = tid; x < TILE_Q; x += SCAN_THREADS) { cnt[x] = 0; tau[x] = FX_INF; }
     if (tid == 0) *flag = 0;
 
-    // per-lane byte offsets of this wave's 4 A blocks and 4 B blocks inside a
-    // tile (fragment-ordered image: block bi = 16-row block * 2 + 64-B half)
-    int offs[4];
+    // per finished tile: filter against tau, push into the LDS lists.  (always_inline: the epilogue must
+    // become part of the loop's body, or the accumulators it reads go through scratch)
+    scan_tiles_128<DT, METRIC>(p, smem, qtile, split, [&](const auto& acc, const auto& yn, int trow0, int rlim, int rl0)
+                                                          __attribute__((always_inline)) {
+        int qloc[4];
+        bool qv[4];
+        float tn[4];
+        unsigned pend[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int bi = wave * 4 + j, rblk = bi >> 1, kb = bi & 1;
-        offs[j] = (rblk * 16 + (lane & 15)) * rb + kb * 64 + (lane >> 4) * 16;
-    }
-    const char* qbase = p.qop + q0 * rb;
-
-    auto issue = [&](int g) {
-        const int t = g / nks, ks = g - t * nks;
-        char* buf = smem + (g & 1) * ((TILE_R + TILE_Q) * STAGE_B);
-        const int64_t row0 = (int64_t)(ct0 + t) * TILE_R;
-        const char* abase = p.codes + row0 * rb + ks * STAGE_B;
-        const char* bbase = qbase + ks * STAGE_B;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            glds16(abase + offs[j], buf + (wave * 4 + j) * 1024);
-            glds16(bbase + offs[j], buf + TILE_R * STAGE_B + (wave * 4 + j) * 1024);
+        for (int n = 0; n < 4; ++n) {
+            qloc[n] = tile_qloc(n);
+            qv[n] = q0 + qloc[n] < nq;
+            tn[n] = tau[qloc[n]];
+            pend[n] = 0u;
         }
-        if (ks == 0 && wave == 0 && lane < 32)
-            glds16(p.norms + row0 + lane * 4, smem + LDS_NORM_OFF + (t & 1) * (TILE_R * 4));
-    };
-
-    f32x4 acc[4][4];
+        int ovf = 0;
 #pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    if (G > 0) issue(0);
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-
-    int t = 0, ks = 0;
-    for (int g = 0; g < G; ++g) {
-        if (g + 1 < G) issue(g + 1);
-        const char* buf = smem + (g & 1) * ((TILE_R + TILE_Q) * STAGE_B);
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            frag_t a[4], b[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) a[m] = *(const frag_t*)(buf + ((wm * 4 + m) * 2 + kb) * 1024 + lane * 16);
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-                b[n] = *(const frag_t*)(buf + TILE_R * STAGE_B + ((wn * 4 + n) * 2 + kb) * 1024 + lane * 16);
+        for (int n = 0; n < 4; ++n)
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
-                for (int n = 0; n < 4; ++n) acc[m][n] = Frag<DT>::mma(a[m], b[n], acc[m][n]);
-        }
-
-        if (ks == nks - 1) {
-            // ---------------- epilogue: filter + push into LDS lists ----------
-            const float* nb = (const float*)(smem + LDS_NORM_OFF + (t & 1) * (TILE_R * 4));
-            const int trow0 = (ct0 + t) * TILE_R;
-            const int rlim = (int)(p.ntotal - (int64_t)trow0);  // rows of this tile that exist
-            const int rl0 = wm * 64 + 4 * (lane >> 4);           // local row of (m=0, i=0)
-            float yn[4][4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                float4 v = *(const float4*)(nb + rl0 + m * 16);
-                yn[m][0] = v.x; yn[m][1] = v.y; yn[m][2] = v.z; yn[m][3] = v.w;
-            }
-            int qloc[4];
-            bool qv[4];
-            float tn[4];
-            unsigned pend[4];
+                for (int i = 0; i < 4; ++i) {
+                    const float v = METRIC == L2 ? acc[m][n][i] + yn[m][i] : acc[m][n][i];
+                    const int rl = tile_rloc(rl0, m, i);
+                    if (qv[n] && rl < rlim && v <= tn[n]) {
+                        const int s = atomicAdd(&cnt[qloc[n]], 1);
+                        if (s < CAP) {
+                            lst_d[qloc[n] * CAP + s] = v;
+                            lst_i[qloc[n] * CAP + s] = trow0 + rl;
+                        } else {
+                            pend[n] |= 1u << (m * 4 + i);
+                            ovf = 1;
+                        }
+                    }
+                }
+        if (ovf) *flag = 1;
+        __syncthreads();
+        while (*flag) {
+            __syncthreads();
+            if (tid == 0) *flag = 0;
+            compact_full(lst_d, lst_i, cnt, tau, wave, lane);
+            __syncthreads();
+            ovf = 0;
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
-                qloc[n] = wn * 64 + n * 16 + (lane & 15);
-                qv[n] = q0 + qloc[n] < nq;
                 tn[n] = tau[qloc[n]];
-                pend[n] = 0u;
-            }
-            int ovf = 0;
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const float v = METRIC == L2 ? acc[m][n][i] + yn[m][i] : acc[m][n][i];
-                        const int rl = rl0 + m * 16 + i;
-                        if (qv[n] && rl < rlim && v <= tn[n]) {
-                            const int s = atomicAdd(&cnt[qloc[n]], 1);
-                            if (s < CAP) {
-                                lst_d[qloc[n] * CAP + s] = v;
-                                lst_i[qloc[n] * CAP + s] = trow0 + rl;
-                            } else {
-                                pend[n] |= 1u << (m * 4 + i);
-                                ovf = 1;
-                            }
-                        }
-                    }
-            if (ovf) *flag = 1;
-            __syncthreads();
-            while (*flag) {
-                __syncthreads();
-                if (tid == 0) *flag = 0;
-                compact_full(lst_d, lst_i, cnt, tau, wave, lane);
-                __syncthreads();
-                ovf = 0;
-#pragma unroll
-                for (int n = 0; n < 4; ++n) {
-                    tn[n] = tau[qloc[n]];
-#pragma unroll
-                    for (int m = 0; m < 4; ++m)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const unsigned bit = 1u << (m * 4 + i);
-                            if (pend[n] & bit) {
-                                const float v =
-                                    METRIC == L2 ? acc[m][n][i] + yn[m][i] : acc[m][n][i];
-                                pend[n] &= ~bit;
-                                if (v <= tn[n]) {
-                                    const int s = atomicAdd(&cnt[qloc[n]], 1);
-                                    if (s < CAP) {
-                                        lst_d[qloc[n] * CAP + s] = v;
-                                        lst_i[qloc[n] * CAP + s] = trow0 + rl0 + m * 16 + i;
-                                    } else {
-                                        pend[n] |= bit;
-                                        ovf = 1;
-                                    }
+                        const unsigned bit = 1u << (m * 4 + i);
+                        if (pend[n] & bit) {
+                            const float v = METRIC == L2 ? acc[m][n][i] + yn[m][i] : acc[m][n][i];
+                            pend[n] &= ~bit;
+                            if (v <= tn[n]) {
+                                const int s = atomicAdd(&cnt[qloc[n]], 1);
+                                if (s < CAP) {
+                                    lst_d[qloc[n] * CAP + s] = v;
+                                    lst_i[qloc[n] * CAP + s] = trow0 + tile_rloc(rl0, m, i);
+                                } else {
+                                    pend[n] |= bit;
+                                    ovf = 1;
                                 }
                             }
                         }
-                }
-                if (ovf) *flag = 1;
-                __syncthreads();
+                    }
             }
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-            ks = 0;
-            ++t;
-        } else {
-            ++ks;
+            if (ovf) *flag = 1;
+            __syncthreads();
         }
-        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    }
+    });
 
     // final flush: sorted top-KP per query of this (query tile, split)
     __syncthreads();
@@ -1491,13 +1414,10 @@ hipError_t launch_centre_norms(const char* codes, int dt, int row_bytes, int64_t
                                float* cnorms, unsigned* cmax_bits, hipStream_t s) {
     if (r1 <= r0) return hipSuccess;
     const dim3 g(grid_for(r1 - r0, 4, ROWS_GRID_CAP));
-    if (dt == BF16)
-        hipLaunchKernelGGL(k_centre_norms<BF16>, g, dim3(256), 0, s, codes, row_bytes, r0, r1, mu, cnorms, cmax_bits);
-    else if (dt == F16)
-        hipLaunchKernelGGL(k_centre_norms<F16>, g, dim3(256), 0, s, codes, row_bytes, r0, r1, mu, cnorms, cmax_bits);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
+    return dispatch_dt_metric<DT_16BIT>(dt, L2, [&](auto dtc, auto) {
+        hipLaunchKernelGGL(k_centre_norms<dtc()>, g, dim3(256), 0, s, codes, row_bytes, r0, r1, mu, cnorms, cmax_bits);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_prep_queries(const PrepParams& p, hipStream_t s) {
@@ -1509,39 +1429,18 @@ hipError_t launch_prep_queries(const PrepParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int DT, int METRIC>
-static hipError_t scan_t(const ScanParams& p, hipStream_t s) {
-    // > 64 KiB of dynamic LDS must be opted into (per device; cheap to repeat)
-    hipError_t e = g_graph_capture ? hipSuccess : hipFuncSetAttribute((const void*)k_scan_topk<DT, METRIC>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS_SCAN_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_scan_topk<DT, METRIC>), dim3(p.grid), dim3(SCAN_THREADS), LDS_SCAN_BYTES, s, p);
-    return hipGetLastError();
-}
-
 hipError_t launch_scan(int st_dt, int metric, const ScanParams& p, hipStream_t s) {
     if (p.tr == V5_TR) return launch_scan_v5(st_dt, metric, p, s);  // (the plan chose k_scan_v5)
     if (p.qt != TILE_Q || p.tr != TILE_R) return hipErrorInvalidValue;
     // the MFMA scan (fx_scan.hip) covers every row width it has a register
     // layout for; other widths take the generic kernel above
-    if (st_dt == F32S) {  // the split-fp32 operand exists only for the MFMA scans
-        bool handled = false;
-        hipError_t e = launch_scan_mfma(st_dt, metric, p, s, &handled);
-        return handled ? e : hipErrorInvalidValue;
-    }
-    {
-        bool handled = false;
-        hipError_t e = launch_scan_mfma(st_dt, metric, p, s, &handled);
-        if (handled) return e;
-    }
-    if (metric == L2) {
-        if (st_dt == F32) return scan_t<F32, L2>(p, s);
-        if (st_dt == BF16) return scan_t<BF16, L2>(p, s);
-        return scan_t<F16, L2>(p, s);
-    }
-    if (st_dt == F32) return scan_t<F32, IP>(p, s);
-    if (st_dt == BF16) return scan_t<BF16, IP>(p, s);
-    return scan_t<F16, IP>(p, s);
+    bool handled = false;
+    hipError_t e = launch_scan_mfma(st_dt, metric, p, s, &handled);
+    if (handled) return e;
+    // (DT_STORED: the split-fp32 operand exists only for the MFMA scans)
+    return dispatch_dt_metric<DT_STORED>(st_dt, metric, [&](auto dt, auto mt) {
+        return launch_with_lds(k_scan_topk<dt(), mt()>, p.grid, SCAN_THREADS, LDS_SCAN_BYTES, s, p);
+    });
 }
 
 template <int DT, int METRIC>
@@ -1562,36 +1461,18 @@ static hipError_t refine_t(const RefineParams& p, hipStream_t s) {
 }
 
 hipError_t launch_refine(int st_dt, int metric, const RefineParams& p, hipStream_t s) {
-    if (metric == L2) {
-        if (st_dt == F32) return refine_t<F32, L2>(p, s);
-        if (st_dt == BF16) return refine_t<BF16, L2>(p, s);
-        return refine_t<F16, L2>(p, s);
-    }
-    if (st_dt == F32) return refine_t<F32, IP>(p, s);
-    if (st_dt == BF16) return refine_t<BF16, IP>(p, s);
-    return refine_t<F16, IP>(p, s);
-}
-
-template <int DT, int METRIC>
-static void fb_t(hipStream_t s, const char* codes, int row_bytes, int kdim, int64_t ntotal, const float* qf32,
-                 const int* n_flag, int k, float* cd, int* ci) {
-    hipLaunchKernelGGL((k_fb_scan<DT, METRIC>), dim3(FB_SCAN_GRID), dim3(BT_THREADS), 0, s, codes, row_bytes, kdim,
-                       ntotal, qf32, n_flag, k, cd, ci);
+    return dispatch_dt_metric<DT_STORED>(st_dt, metric,
+                                         [&](auto dt, auto mt) { return refine_t<dt(), mt()>(p, s); });
 }
 
 hipError_t launch_exact_fallback(int st_dt, int metric, const char* codes, int row_bytes, int kdim, int64_t ntotal,
                                  const float* qf32, const int* n_flag, int k, int64_t id_offset, float* cand_d,
                                  int* cand_i, float* D, int64_t* I, hipStream_t s) {
-    if (metric == L2) {
-        if (st_dt == F32) fb_t<F32, L2>(s, codes, row_bytes, kdim, ntotal, qf32, n_flag, k, cand_d, cand_i);
-        else if (st_dt == BF16) fb_t<BF16, L2>(s, codes, row_bytes, kdim, ntotal, qf32, n_flag, k, cand_d, cand_i);
-        else fb_t<F16, L2>(s, codes, row_bytes, kdim, ntotal, qf32, n_flag, k, cand_d, cand_i);
-    } else {
-        if (st_dt == F32) fb_t<F32, IP>(s, codes, row_bytes, kdim, ntotal, qf32, n_flag, k, cand_d, cand_i);
-        else if (st_dt == BF16) fb_t<BF16, IP>(s, codes, row_bytes, kdim, ntotal, qf32, n_flag, k, cand_d, cand_i);
-        else fb_t<F16, IP>(s, codes, row_bytes, kdim, ntotal, qf32, n_flag, k, cand_d, cand_i);
-    }
-    hipError_t e = hipGetLastError();
+    hipError_t e = dispatch_dt_metric<DT_STORED>(st_dt, metric, [&](auto dt, auto mt) {
+        hipLaunchKernelGGL((k_fb_scan<dt(), mt()>), dim3(FB_SCAN_GRID), dim3(BT_THREADS), 0, s, codes, row_bytes, kdim,
+                           ntotal, qf32, n_flag, k, cand_d, cand_i);
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return e;
     if (metric == L2)
         hipLaunchKernelGGL(k_fb_merge<L2>, dim3(FB_MERGE_GRID), dim3(BT_THREADS), 0, s, n_flag, ntotal, k, cand_d,

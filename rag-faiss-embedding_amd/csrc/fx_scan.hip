@@ -742,12 +742,7 @@ static hipError_t scan_v4_t(const ScanParams& p, hipStream_t s) {
     }
 #endif
     constexpr int LDS_BYTES = ScanLds<ring_slots<KSTEPS>()>::BYTES;
-    hipError_t e = g_graph_capture ? hipSuccess
-                                   : hipFuncSetAttribute((const void*)k_scan_v4<DT, METRIC, KSTEPS, ABL, LN>,
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_scan_v4<DT, METRIC, KSTEPS, ABL, LN>), dim3(p.grid), dim3(SCAN_THREADS), LDS_BYTES, s, p);
-    return hipGetLastError();
+    return launch_with_lds(k_scan_v4<DT, METRIC, KSTEPS, ABL, LN>, p.grid, SCAN_THREADS, LDS_BYTES, s, p);
 }
 
 template <int DT, int METRIC>
@@ -779,15 +774,8 @@ hipError_t launch_scan_mfma(int st_dt, int metric, const ScanParams& p, hipStrea
         *handled = false;
         return hipSuccess;
     }
-    if (st_dt == F32S) return metric == L2 ? scan_rows<F32S, L2>(p, s, handled) : scan_rows<F32S, IP>(p, s, handled);
-    if (metric == L2) {
-        if (st_dt == F32) return scan_rows<F32, L2>(p, s, handled);
-        if (st_dt == BF16) return scan_rows<BF16, L2>(p, s, handled);
-        return scan_rows<F16, L2>(p, s, handled);
-    }
-    if (st_dt == F32) return scan_rows<F32, IP>(p, s, handled);
-    if (st_dt == BF16) return scan_rows<BF16, IP>(p, s, handled);
-    return scan_rows<F16, IP>(p, s, handled);
+    return dispatch_dt_metric<DT_SCAN>(st_dt, metric,
+                                       [&](auto dt, auto mt) { return scan_rows<dt(), mt()>(p, s, handled); });
 }
 
 }  // namespace fx

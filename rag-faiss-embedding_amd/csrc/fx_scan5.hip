@@ -696,13 +696,7 @@ __global__ __launch_bounds__(SCAN_THREADS, 1) void k_scan_v5(ScanParams p) {
 template <int DT, int METRIC, int KSTEPS, int NB, int LC, int ABL>
 static hipError_t launch_t(const ScanParams& p, hipStream_t s) {
     constexpr int LDS_BYTES = Lds<NB, LC, ns_for<KSTEPS, NB>()>::BYTES;
-    hipError_t e = g_graph_capture ? hipSuccess
-                                   : hipFuncSetAttribute((const void*)k_scan_v5<DT, METRIC, KSTEPS, NB, LC, ABL>,
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_scan_v5<DT, METRIC, KSTEPS, NB, LC, ABL>), dim3(p.grid), dim3(SCAN_THREADS), LDS_BYTES, s,
-                       p);
-    return hipGetLastError();
+    return launch_with_lds(k_scan_v5<DT, METRIC, KSTEPS, NB, LC, ABL>, p.grid, SCAN_THREADS, LDS_BYTES, s, p);
 }
 
 template <int DT, int METRIC>
@@ -749,8 +743,7 @@ int scan_v5_qt(int st_dt, int row_bytes) {
 hipError_t launch_scan_v5(int st_dt, int metric, const ScanParams& p, hipStream_t s) {
     if (scan_v5_qt(st_dt, p.row_bytes) == 0 || p.qt != scan_v5_qt(st_dt, p.row_bytes) || p.tr != v5::TR)
         return hipErrorInvalidValue;
-    if (metric == L2) return st_dt == BF16 ? v5::rows<BF16, L2>(p, s) : v5::rows<F16, L2>(p, s);
-    return st_dt == BF16 ? v5::rows<BF16, IP>(p, s) : v5::rows<F16, IP>(p, s);
+    return dispatch_dt_metric<DT_16BIT>(st_dt, metric, [&](auto dt, auto mt) { return v5::rows<dt(), mt()>(p, s); });
 }
 
 }  // namespace fx
