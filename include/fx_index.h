@@ -16,6 +16,9 @@
  *   index.range_search    (score >= s filter of      faiss_Index_range_search     fx_index_range_search
  *     (x, radius)          query.py:42,                                            + fx_index_range_result
  *                          2-cli-rag-search.py:48)
+ *   index.search(x, k,    (a query restricted to     faiss_Index_search_with_     fx_index_search_sel
+ *     params=...)          one document set; see      params                      + fx_selector_create
+ *                          "filtered search" below)
  *   index.ntotal          faiss_store.py:53          faiss_Index_ntotal           fx_index_ntotal
  *   (re)IndexFlatL2(d)    faiss_store.py:126         faiss_Index_reset            fx_index_reset
  *   faiss.write_index     faiss_store.py:91,         faiss_write_index_fname      fx_index_write
@@ -180,6 +183,61 @@ int fx_index_range_result(FxIndex* index, float* D, int64_t* I, int out_mem);
  * result count; the exact pass removed the rest) and scan passes run (1, or
  * 2 when the candidate buffer had to grow; 0 when no scan was needed). */
 int fx_index_last_range_stats(FxIndex* index, int64_t* candidates, int* passes);
+
+/* ---- filtered search: faiss IDSelector / SearchParameters ---------------
+ *
+ *   faiss (Python)                                  faiss C API                        this ABI
+ *   IDSelectorBatch / IDSelectorArray(ids)          faiss_IDSelectorBatch_new          fx_selector_create(FX_SEL_IDS)
+ *   IDSelectorBitmap(n, bitmap)                     faiss_IDSelectorBitmap_new         fx_selector_create(FX_SEL_BITMAP)
+ *   IDSelectorRange(imin, imax)                     faiss_IDSelectorRange_new          fx_selector_create(FX_SEL_RANGE)
+ *   IDSelectorNot(sel)                              faiss_IDSelectorNot_new            the `invert` argument
+ *   SearchParameters(sel=...)                       faiss_SearchParameters_new         (the selector handle itself)
+ *   index.search(x, k, params=...)                  faiss_Index_search_with_params     fx_index_search_sel
+ *   (GC of the selector)                            faiss_IDSelector_free              fx_selector_free
+ *
+ * Ids are the ids search returns: local row r has id r + id_offset
+ * (fx_index_set_id_offset).  A selector is a SNAPSHOT of the index's rows
+ * [0, ntotal) at creation: it owns a device row mask (one bit per row) and the
+ * ascending list of the 128-row tiles that hold a selected row; the filtered
+ * scan visits those tiles only, and rows that are not selected never become
+ * candidates.  After rows are added or the index is reset the snapshot no
+ * longer describes the index: create a new selector. */
+typedef struct FxSelector FxSelector;
+enum { FX_SEL_BITMAP = 0, FX_SEL_IDS = 1, FX_SEL_RANGE = 2 };
+
+/* kind FX_SEL_BITMAP: data = n bytes; id i is a member iff
+ *   data[i >> 3] & (1 << (i & 7)); ids >= 8 n are not members (IDSelectorBitmap).
+ * kind FX_SEL_IDS: data = n int64 ids; duplicates and ids outside the index
+ *   are ignored (IDSelectorArray / IDSelectorBatch).
+ * kind FX_SEL_RANGE: data = two int64 {imin, imax} in HOST memory whatever
+ *   data_mem says (n is ignored); members are imin <= id < imax
+ *   (IDSelectorRange).
+ * invert != 0 selects the complement within the index's rows (IDSelectorNot).
+ * data_mem: FX_MEM_HOST, or FX_MEM_DEVICE -- device data is read stream-ordered
+ * on the index's stream and must stay valid until that work has run.  data may
+ * be NULL when n == 0 (bitmap, ids).  FX_E_ARG: null index / out, a kind other
+ * than the three (named in the message), n < 0, imax < imin. */
+int fx_selector_create(FxIndex* index, int kind, const void* data, int64_t n, int data_mem, int invert,
+                       FxSelector** out);
+/* May be called after the index was freed. */
+void fx_selector_free(FxSelector* sel);
+/* Selected rows and live 128-row tiles of the snapshot (synchronises with the
+ * selector's build when it was created from device data). */
+int fx_selector_stats(const FxSelector* sel, int64_t* rows, int64_t* tiles);
+/* fx_index_search over the selector's rows only: the k nearest SELECTED rows
+ * of every query; with fewer than k selected rows the missing slots hold
+ * I = -1, D = +-FLT_MAX, as an index with that many rows returns; an empty
+ * selection pads every slot (no scan is launched).  Argument rules (nq == 0,
+ * k <= 0, dtypes, buffers) and the host / device output modes are
+ * fx_index_search's; results are exact in the same sense (every stage --
+ * scan, certification, re-scan, exact fallback -- sees the same subset).
+ * FX_E_ARG: a selector created on another index, or a stale one (the index's
+ * ntotal differs from the snapshot's: rows were added or the index reset
+ * since).  k > FX_MAX_K: FX_E_UNSUPPORTED (the exact sort path takes no
+ * selector).  Never replayed from a search graph.  The fx_index_last_*
+ * calls report a filtered search like any other. */
+int fx_index_search_sel(FxIndex* index, const FxSelector* sel, int64_t nq, const void* q, int q_dtype, int q_mem,
+                        int k, float* D, int64_t* I, int out_mem);
 
 /* Number of queries of the last search whose top-k could not be certified
  * from the scan's candidate margin and were re-scanned with a wide candidate

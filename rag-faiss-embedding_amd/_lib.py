@@ -57,6 +57,10 @@ SIGNATURES = {
     "fx_index_range_search": (_i, [_vp, _i64, _vp, _i, _i, ctypes.c_float, _vp]),
     "fx_index_range_result": (_i, [_vp, _vp, _vp, _i]),
     "fx_index_last_range_stats": (_i, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i)]),
+    "fx_selector_create": (_i, [_vp, _i, _vp, _i64, _i, _i, _pp]),
+    "fx_selector_free": (None, [_vp]),
+    "fx_selector_stats": (_i, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "fx_index_search_sel": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _vp, _vp, _i]),
     "fx_index_last_fallbacks": (_i, [_vp, ctypes.POINTER(_i64)]),
     "fx_index_last_scan_plan": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "fx_index_last_exact_fallbacks": (_i, [_vp, ctypes.POINTER(_i64)]),

@@ -1,5 +1,6 @@
 // fx_device.h -- device-side helpers shared by the HIP translation units
-// (fx_kernels.hip, fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip):
+// (fx_kernels.hip, fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip,
+// fx_select.hip):
 // conversions, the exact fp64 distance, wave sorts and sums, block placement,
 // the block top-K, the plain scans' tile loop (scan_tiles_128) and the MFMA
 // wrappers of k_scan_v4 / k_scan_v5.  Header-only, all inline.
@@ -449,13 +450,30 @@ __device__ __forceinline__ int tile_rloc(int rl0, int m, int i) { return rl0 + m
 // acc[m][n][i] + yn[m][i] for L2 and acc[m][n][i] for IP: an IP scan never
 // reads the row norms, so their DMA is not issued and yn is 0.  What the
 // caller wrote to LDS before the call is visible to every thread inside ep.
-template <int DT, int METRIC, class Epilogue>
-__device__ __forceinline__ void scan_tiles_128(const ScanParams& p, char* smem, int qtile, int split, Epilogue&& ep) {
+// LIVE (the filtered scan, fx_select.hip): the split's tile range is taken
+// over the ascending list `tiles` of the *n_live tiles that hold a selected
+// row (the count is read on the device: clustered selections keep their
+// splits balanced, and the host plans without it); tile t's rows start at
+// tiles[ct0 + t] * TILE_R, which is the trow0 ep sees.  A split that gets no
+// tile calls ep never.  Without LIVE both pointers are unused.
+template <int DT, int METRIC, bool LIVE = false, class Epilogue>
+__device__ __forceinline__ void scan_tiles_128(const ScanParams& p, char* smem, int qtile, int split, Epilogue&& ep,
+                                               const int* __restrict__ tiles = nullptr,
+                                               const int* __restrict__ n_live = nullptr) {
     typedef typename Frag<DT>::T frag_t;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int ct0 = (int)((int64_t)split * p.n_ctiles / p.splits);
-    const int ct1 = (int)((int64_t)(split + 1) * p.n_ctiles / p.splits);
+    // tiles to divide among the splits, and the index's tile that is the split's tile t
+    auto tile_count = [&]() -> int {
+        if constexpr (LIVE) return min(max(__builtin_amdgcn_readfirstlane(*n_live), 0), p.n_ctiles);
+        else return p.n_ctiles;
+    };
+    const int ct0 = (int)((int64_t)split * tile_count() / p.splits);
+    const int ct1 = (int)((int64_t)(split + 1) * tile_count() / p.splits);
+    auto tile_of = [&](int t) -> int {
+        if constexpr (LIVE) return __builtin_amdgcn_readfirstlane(tiles[ct0 + t]);
+        else return ct0 + t;
+    };
     const int nks = p.row_bytes / STAGE_B;
     const int G = (ct1 - ct0) * nks;
     const int rb = p.row_bytes;
@@ -473,7 +491,7 @@ __device__ __forceinline__ void scan_tiles_128(const ScanParams& p, char* smem, 
     auto issue = [&](int g) {
         const int t = g / nks, ks = g - t * nks;
         char* buf = smem + (g & 1) * ((TILE_R + TILE_Q) * STAGE_B);
-        const int64_t row0 = (int64_t)(ct0 + t) * TILE_R;
+        const int64_t row0 = (int64_t)tile_of(t) * TILE_R;
         const char* abase = p.codes + row0 * rb + ks * STAGE_B;
         const char* bbase = qbase + ks * STAGE_B;
 #pragma unroll
@@ -514,7 +532,7 @@ __device__ __forceinline__ void scan_tiles_128(const ScanParams& p, char* smem, 
 
         if (__builtin_expect(ks == nks - 1, 0)) {  // (the stage loop is the straight path)
             const float* nb = (const float*)(smem + LDS_NORM_OFF + (t & 1) * (TILE_R * 4));
-            const int trow0 = (ct0 + t) * TILE_R;
+            const int trow0 = tile_of(t) * TILE_R;
             const int rlim = (int)(p.ntotal - (int64_t)trow0);  // rows of this tile that exist
             const int rl0 = wm * 64 + 4 * (lane >> 4);           // local row of (m = 0, i = 0)
             float yn[4][4];

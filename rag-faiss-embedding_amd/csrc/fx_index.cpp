@@ -263,6 +263,8 @@ struct SearchPlan {
     PrepParams pp2{};
     int* n_exact = nullptr;  // queries the re-scan left uncertified too (-> exact scan)
     int nchunks = 0;         // re-scan chunks of <= RESCAN_MAX flagged queries each
+    const FxSelector* sel = nullptr;  // non-null: a filtered search (fx_index_search_sel): the plain plan over
+                                      // the stored rows, every scan through k_scan_topk_sel
     int* chunk_cnt = nullptr;  // [nchunks] live queries of each chunk (k_rescan_chunks, on the device)
 };
 
@@ -346,7 +348,28 @@ struct FxIndex {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_scan, ev_merge;
     std::mutex mu;
 
+    uint64_t epoch = 0;  // bumped by reset: a selector (a snapshot of the rows) from before is stale
+
     hipStream_t stream() const { return user_stream ? user_stream : own_stream; }
+};
+
+// A selector (include/fx_index.h): the device image fx_select.hip builds of a
+// subset of `index`'s rows [0, ntotal) as they were at creation.
+struct FxSelector {
+    const FxIndex* index = nullptr;  // identity only (never dereferenced: the index may be freed first)
+    int device = 0;
+    int64_t ntotal = 0;
+    uint64_t epoch = 0;
+    uint32_t* mask = nullptr;   // sel_mask_words(ntotal) words
+    int* tiles = nullptr;       // [ceil(ntotal / TILE_R)] ascending live tiles
+    SelCounts* cnt = nullptr;   // device counts (the scan reads cnt->tiles)
+    // the counts on the host: copied stream-ordered into pinned memory after
+    // the build, read (after `ready`) the first time someone asks
+    SelCounts* pin = nullptr;
+    hipEvent_t ready = nullptr;
+    mutable bool known = false;
+    mutable int64_t rows = 0, ntiles = 0;
+    mutable std::mutex mu;
 };
 
 namespace {
@@ -510,6 +533,38 @@ void plan_scan(const FxIndex* h, int64_t nq, int k, ScanParams& p) {
     if (v5) p.tight_at = 0;  // (k_scan_v5 has no between-compaction re-bound)
 }
 
+// The plan of a filtered search (k_scan_topk_sel), whatever the index's scan
+// image: 128 x 128 tiles over the stored rows, sized and placed from the
+// shape alone as the range filter's grid is (plan_range_scan) -- over ALL the
+// index's tiles, an upper bound of the selector's live ones, which the kernel
+// divides among the splits on the device.  No cross-split sharing; k > KP
+// takes at least k/4 splits like plan_scan, so that the splits' KP-entry
+// lists can hold k results.
+void plan_sel_scan(const FxIndex* h, int64_t nq, int k, ScanParams& p) {
+    p.qt = TILE_Q;
+    p.tr = TILE_R;
+    p.n_qtiles = (int)((nq + TILE_Q - 1) / TILE_Q);
+    p.n_ctiles = (int)((h->ntotal + TILE_R - 1) / TILE_R);
+    constexpr int min_tiles = 3;
+    SplitPlan sp = plan_splits(p.n_qtiles, p.n_ctiles, min_tiles, true, false);
+    if (k > KP) {
+        if (sp.place == 1) {
+            const int max_sx = std::max(1, p.n_ctiles / (8 * min_tiles));
+            sp.sx = std::max(sp.sx, std::min(max_sx, ((k + 3) / 4 + 7) / 8));
+            sp.splits = 8 * sp.sx;
+        } else {
+            sp.splits = std::max(sp.splits, std::min(std::max(1, p.n_ctiles / min_tiles), (k + 3) / 4));
+        }
+    }
+    sp.store(p);
+    p.share = 0;
+    p.pub = nullptr;
+    p.prune_rank = KP;
+    p.compact_at = CAP;
+    p.union_w = 16;
+    p.union_defer = p.union_inplace = p.tight_at = p.cold_bound = 0;
+}
+
 // k > KP: approx candidates the refine re-ranks exactly (k_refine_big)
 int big_k1(int k) { return k > KP ? std::max(2 * k, 64) : 0; }
 
@@ -607,7 +662,8 @@ hipError_t plan_rescan(FxIndex* h, SearchPlan& P) {
     ScanParams& sp = P.sp2;
     sp = P.sp;
     sp.nq = nq;
-    plan_scan(h, nq, k1, sp);  // k1 > KP: share = 0, >= k1/4 splits
+    if (P.sel) plan_sel_scan(h, nq, k1, sp);  // (a filtered search re-scans with its own kernel)
+    else plan_scan(h, nq, k1, sp);  // k1 > KP: share = 0, >= k1/4 splits
     const int64_t nq_pad = round_up(nq, std::max<int64_t>(QPAD, sp.qt));
     if ((e = h->rq_f32.ensure((size_t)nq_pad * h->kdim * 4)) != hipSuccess) return e;
     if ((e = h->rq_op.ensure((size_t)nq_pad * h->row_bytes)) != hipSuccess) return e;
@@ -678,14 +734,17 @@ hipError_t plan_search(FxIndex* h, int64_t nq, const void* qdev, int q_dtype, in
     P.nq = nq;
     P.k = k;
     P.q_dtype = q_dtype;
-    P.scan_dt = h->img_kind == IMG_F32S ? (int)F32S : h->dtype;
+    // a filtered search scans the stored rows themselves (no image)
+    const int img_kind = P.sel ? (int)IMG_NONE : h->img_kind;
+    P.scan_dt = img_kind == IMG_F32S ? (int)F32S : h->dtype;
     ScanParams& sp = P.sp;
-    plan_scan(h, nq, k, sp);
+    if (P.sel) plan_sel_scan(h, nq, k, sp);
+    else plan_scan(h, nq, k, sp);
     h->last_plan[0] = sp.tr;
     h->last_plan[1] = sp.qt;
     h->last_plan[2] = sp.splits;
     P.nq_pad = round_up(nq, std::max<int64_t>(QPAD, sp.qt));  // whole scan tiles of (zero) queries
-    const bool img = h->img_kind != IMG_NONE;
+    const bool img = img_kind != IMG_NONE;
     if ((e = h->qf32.ensure((size_t)P.nq_pad * h->kdim * 4)) != hipSuccess) return e;
     if ((e = h->qop.ensure((size_t)P.nq_pad * h->row_bytes)) != hipSuccess) return e;
     if ((e = h->qeps.ensure((size_t)nq * 4)) != hipSuccess) return e;
@@ -712,20 +771,20 @@ hipError_t plan_search(FxIndex* h, int64_t nq, const void* qdev, int q_dtype, in
     pp.qidx = nullptr;
     pp.nq_dev = nullptr;
 
-    sp.codes = h->img_kind == IMG_F32S ? (const char*)h->split.p : h->codes;
+    sp.codes = img_kind == IMG_F32S ? (const char*)h->split.p : h->codes;
     sp.norms = img ? (const float*)h->cnorms.p : h->norms;
     sp.ntotal = h->ntotal;
     sp.row_bytes = h->row_bytes;
     sp.qop = (const char*)h->qop.p;
     sp.nq = nq;
-    sp.dbg = h->opt.scan_dbg;
+    sp.dbg = P.sel ? 0 : h->opt.scan_dbg;
     if ((e = h->gtau.ensure((size_t)P.nq_pad * 4)) != hipSuccess) return e;
     sp.gtau = (unsigned*)h->gtau.p;
     sp.conv = nullptr;
     // (only grids of more than one dispatch round: a single round's blocks
     // start together, and the word's read would only add a round trip to
     // the one-query call)
-    if (h->opt.convoy != 0 && sp.grid > 256 && sp.splits <= CONV_MAX) {
+    if (!P.sel && h->opt.convoy != 0 && sp.grid > 256 && sp.splits <= CONV_MAX) {
         if (!h->conv.p) {
             if ((e = h->conv.ensure((size_t)CONV_WORDS * 4)) != hipSuccess) return e;
             if ((e = hipMemsetAsync(h->conv.p, 0, (size_t)CONV_WORDS * 4, h->stream())) != hipSuccess) return e;
@@ -802,6 +861,13 @@ hipError_t plan_search(FxIndex* h, int64_t nq, const void* qdev, int q_dtype, in
     return plan_rescan(h, P);
 }
 
+// the scan of a plan (pass 1's or the re-scan's parameters): the filtered
+// kernel when the search has a selector
+hipError_t run_scan(const FxIndex* h, const SearchPlan& P, const ScanParams& sp, hipStream_t s) {
+    if (P.sel) return launch_scan_sel(h->dtype, h->metric, sp, P.sel->mask, P.sel->tiles, P.sel->cnt, s);
+    return launch_scan(P.scan_dt, h->metric, sp, s);
+}
+
 // Enqueue the planned search on s up to its certification: query preparation
 // (which also resets the shared thresholds, the published lists and the
 // search's counters: one kernel instead of memsets), scan, refine +
@@ -819,7 +885,7 @@ hipError_t enqueue_main(FxIndex* h, SearchPlan& P, hipStream_t s, bool timed, hi
     pp1.npub = P.sp.pub ? P.nq * P.sp.splits * KP : 0;
     if ((e = launch_prep_queries(pp1, s)) != hipSuccess) return e;
     if (timed && (e = hipEventRecord(ev[0], s)) != hipSuccess) return e;
-    if ((e = launch_scan(P.scan_dt, h->metric, P.sp, s)) != hipSuccess) return e;
+    if ((e = run_scan(h, P, P.sp, s)) != hipSuccess) return e;
     if (timed && (e = hipEventRecord(ev[1], s)) != hipSuccess) return e;
     RefineParams rp = P.rp;
     if (P.reduce) {
@@ -864,12 +930,12 @@ hipError_t enqueue_fallback(FxIndex* h, SearchPlan& P, hipStream_t s) {
         rp2.nq_dev = P.chunk_cnt + c;
         rp2.out_idx = list;
         if ((e = launch_prep_queries(pp, s)) != hipSuccess) return e;
-        if ((e = launch_scan(P.scan_dt, h->metric, sp, s)) != hipSuccess) return e;
+        if ((e = run_scan(h, P, sp, s)) != hipSuccess) return e;
         if ((e = launch_refine(h->dtype, h->metric, rp2, s)) != hipSuccess) return e;
     }
     return launch_exact_fallback(h->dtype, h->metric, h->codes, h->row_bytes, h->kdim, h->ntotal, P.rp.qf32,
                                  P.n_exact, P.k, h->id_offset, (float*)h->fbc_d.p, (int*)h->fbc_i.p, P.rp.D, P.rp.I,
-                                 s);
+                                 s, P.sel ? P.sel->mask : nullptr);
 }
 
 // Host-output searches (the reference's call form) return through ONE packed
@@ -964,7 +1030,7 @@ int finish_host_out(FxIndex* h, SearchPlan& P, const HostOut& L, char* pin, floa
 constexpr size_t QPIN_MAX = (size_t)4 << 20;
 
 int do_search(FxIndex* h, int64_t nq, const void* q, int q_dtype, int q_mem, int k, float* D, int64_t* I,
-              int out_mem) {
+              int out_mem, const FxSelector* sel = nullptr) {
     hipStream_t s = h->stream();
     const int qes = dtype_size(q_dtype);
     // queries -> device
@@ -994,8 +1060,9 @@ int do_search(FxIndex* h, int64_t nq, const void* q, int q_dtype, int q_mem, int
         Id = (int64_t*)((char*)h->hout.p + L.offI);
         words = (int*)((char*)h->hout.p + L.offW);
     }
-    HIP_TRY(update_scan_image(h));
+    if (!sel) HIP_TRY(update_scan_image(h));  // (a filtered search reads no image)
     SearchPlan P;
+    P.sel = sel;
     HIP_TRY(plan_search(h, nq, qdev, q_dtype, k, Dd, Id, words, P));
 #ifdef FX_DIAG
     // diagnostics (Options): per-block placement/timing, phase stamps, the
@@ -1230,6 +1297,38 @@ int graph_search(FxIndex* h, int64_t nq, const void* q, int q_dtype, int k, floa
     return rc;
 }
 
+// every slot missing (I = -1, D = FLT_MAX; IP: -FLT_MAX): the search of an
+// empty index, or of an empty selection
+int fill_missing(FxIndex* h, int64_t nq, int k, float* D, int64_t* I, int out_mem) {
+    const float dfill = h->metric == L2 ? FLT_MAX : -FLT_MAX;
+    if (out_mem == FX_MEM_HOST) {
+        std::fill(D, D + (size_t)nq * k, dfill);
+        std::fill(I, I + (size_t)nq * k, (int64_t)-1);
+    } else {  // stream-ordered fills: -1 is all ones in two's complement
+        uint32_t bits;
+        memcpy(&bits, &dfill, 4);
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)D, bits, (size_t)nq * k, h->stream()));
+        HIP_TRY(hipMemsetAsync(I, 0xff, (size_t)nq * k * 8, h->stream()));
+    }
+    h->last_fallbacks = 0;
+    h->last_exact = 0;
+    h->last_dropped = 0;
+    h->fb_pending = false;
+    return FX_OK;
+}
+
+// the selector's counts on the host (waits for its build once)
+int selector_counts(const FxSelector* sel) {
+    std::lock_guard<std::mutex> lk(sel->mu);
+    if (sel->known) return FX_OK;
+    DeviceGuard g(sel->device);
+    HIP_TRY(hipEventSynchronize(sel->ready));
+    sel->rows = sel->pin->rows;
+    sel->ntiles = sel->pin->tiles;
+    sel->known = true;
+    return FX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1438,24 +1537,7 @@ int fx_index_search(FxIndex* h, int64_t nq, const void* q, int q_dtype, int q_me
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
     if (h->ntotal > 0 && k > FX_MAX_K) return do_search_hugek(h, nq, q, q_dtype, q_mem, k, D, I, out_mem);
-    if (h->ntotal == 0) {
-        // faiss: empty index -> every slot missing (I = -1, D = FLT_MAX)
-        const float dfill = h->metric == L2 ? FLT_MAX : -FLT_MAX;
-        if (out_mem == FX_MEM_HOST) {
-            std::fill(D, D + (size_t)nq * k, dfill);
-            std::fill(I, I + (size_t)nq * k, (int64_t)-1);
-        } else {  // stream-ordered fills: -1 is all ones in two's complement
-            uint32_t bits;
-            memcpy(&bits, &dfill, 4);
-            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)D, bits, (size_t)nq * k, h->stream()));
-            HIP_TRY(hipMemsetAsync(I, 0xff, (size_t)nq * k * 8, h->stream()));
-        }
-        h->last_fallbacks = 0;
-        h->last_exact = 0;
-        h->last_dropped = 0;
-        h->fb_pending = false;
-        return FX_OK;
-    }
+    if (h->ntotal == 0) return fill_missing(h, nq, k, D, I, out_mem);  // faiss: empty index -> every slot missing
     const Options& o = h->opt;
 #ifdef FX_DIAG
     const bool diag = o.scan_dbg != 0 || !o.trace.empty() || !o.cand.empty() || !o.stamps.empty();
@@ -1466,6 +1548,129 @@ int fx_index_search(FxIndex* h, int64_t nq, const void* q, int q_dtype, int q_me
         h->user_stream == nullptr)
         return graph_search(h, nq, q, q_dtype, k, D, I);
     return do_search(h, nq, q, q_dtype, q_mem, k, D, I, out_mem);
+}
+
+// ---- filtered search (fx_select.hip) ---------------------------------------
+
+void fx_selector_free(FxSelector* sel) {
+    if (!sel) return;
+    {
+        DeviceGuard g(sel->device);
+        if (sel->ready) {
+            (void)hipEventSynchronize(sel->ready);
+            (void)hipEventDestroy(sel->ready);
+        }
+        if (sel->mask) (void)hipFree(sel->mask);
+        if (sel->tiles) (void)hipFree(sel->tiles);
+        if (sel->cnt) (void)hipFree(sel->cnt);
+        if (sel->pin) (void)hipHostFree(sel->pin);
+    }
+    delete sel;
+}
+
+int fx_selector_create(FxIndex* h, int kind, const void* data, int64_t n, int data_mem, int invert,
+                       FxSelector** out) {
+    if (!out) return set_err(FX_E_ARG, "null out");
+    *out = nullptr;
+    if (kind != FX_SEL_BITMAP && kind != FX_SEL_IDS && kind != FX_SEL_RANGE)
+        return set_err(FX_E_ARG, "bad selector kind %d (FX_SEL_BITMAP 0, FX_SEL_IDS 1, FX_SEL_RANGE 2)", kind);
+    if (!h) return set_err(FX_E_ARG, "null index");
+    if (data_mem != FX_MEM_HOST && data_mem != FX_MEM_DEVICE) return set_err(FX_E_ARG, "bad data_mem %d", data_mem);
+    int64_t imin = 0, imax = 0;
+    if (kind == FX_SEL_RANGE) {
+        if (!data) return set_err(FX_E_ARG, "selector: null range");
+        memcpy(&imin, data, 8);
+        memcpy(&imax, (const char*)data + 8, 8);
+        if (imax < imin)
+            return set_err(FX_E_ARG, "selector: range with imax %lld < imin %lld", (long long)imax, (long long)imin);
+    } else {
+        if (n < 0) return set_err(FX_E_ARG, "selector: negative n");
+        if (n > 0 && !data) return set_err(FX_E_ARG, "selector: null data");
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    if (!g.ok) return set_err(FX_E_HIP, "hipSetDevice(%d) failed", h->device);
+    hipStream_t s = h->stream();
+    FxSelector* sel = new FxSelector();
+    sel->index = h;
+    sel->device = h->device;
+    sel->ntotal = h->ntotal;
+    sel->epoch = h->epoch;
+    const int64_t nt = h->ntotal, off = h->id_offset;
+    const int64_t nwords = sel_mask_words(nt), ntiles = nwords / (TILE_R / 32);
+    void* staged = nullptr;  // host data on the device for the build
+    hipError_t e = hipMalloc((void**)&sel->mask, (size_t)std::max<int64_t>(nwords, 4) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&sel->tiles, (size_t)std::max<int64_t>(ntiles, 1) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&sel->cnt, sizeof(SelCounts));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&sel->pin, sizeof(SelCounts), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&sel->ready, hipEventDisableTiming);
+    if (e == hipSuccess && kind == FX_SEL_RANGE) {
+        // ids -> local rows, clamped to the index (id_offset >= 0; differences of int64 ids may not overflow)
+        auto local = [&](int64_t id) { return id <= off ? (int64_t)0 : std::min(id - off, nt); };
+        e = launch_sel_range(local(imin), local(imax), nt, invert != 0, sel->mask, s);
+    } else if (e == hipSuccess) {
+        const size_t bytes = (size_t)n * (kind == FX_SEL_IDS ? 8 : 1);
+        const void* dev = data;
+        if (data_mem == FX_MEM_HOST && n > 0) {
+            e = hipMalloc(&staged, bytes);
+            if (e == hipSuccess) e = hipMemcpyAsync(staged, data, bytes, hipMemcpyHostToDevice, s);
+            dev = staged;
+        }
+        if (e == hipSuccess)
+            e = kind == FX_SEL_IDS ? launch_sel_ids((const int64_t*)dev, n, off, nt, invert != 0, sel->mask, s)
+                                   : launch_sel_bitmap((const uint8_t*)dev, n, off, nt, invert != 0, sel->mask, s);
+    }
+    if (e == hipSuccess) e = launch_sel_tiles(sel->mask, nt, sel->tiles, sel->cnt, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(sel->pin, sel->cnt, sizeof(SelCounts), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipEventRecord(sel->ready, s);
+    if (staged) {  // host data: the build has to finish before the staging copy goes
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        (void)hipFree(staged);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        fx_selector_free(sel);
+        return set_err(FX_E_HIP, "selector build: %s", hipGetErrorString(e));
+    }
+    *out = sel;
+    return FX_OK;
+}
+
+int fx_selector_stats(const FxSelector* sel, int64_t* rows, int64_t* tiles) {
+    if (!sel || !rows || !tiles) return set_err(FX_E_ARG, "null argument");
+    const int rc = selector_counts(sel);
+    if (rc != FX_OK) return rc;
+    *rows = sel->rows;
+    *tiles = sel->ntiles;
+    return FX_OK;
+}
+
+int fx_index_search_sel(FxIndex* h, const FxSelector* sel, int64_t nq, const void* q, int q_dtype, int q_mem, int k,
+                        float* D, int64_t* I, int out_mem) {
+    if (!h) return set_err(FX_E_ARG, "null index");
+    if (!sel) return set_err(FX_E_ARG, "null selector");
+    if (nq < 0) return set_err(FX_E_ARG, "negative nq");
+    if (k <= 0) return set_err(FX_E_ARG, "k must be positive (got %d)", k);
+    if (!check_dtype(q_dtype)) return set_err(FX_E_ARG, "bad query dtype %d", q_dtype);
+    if (sel->index != h) return set_err(FX_E_ARG, "search: the selector was created on another index");
+    if (k > FX_MAX_K)
+        return set_err(FX_E_UNSUPPORTED, "search with a selector supports k <= %d (got %d): the exact sort path takes none",
+                       FX_MAX_K, k);
+    if (nq == 0) return FX_OK;
+    if (!q || !D || !I) return set_err(FX_E_ARG, "null buffer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (sel->ntotal != h->ntotal || sel->epoch != h->epoch)
+        return set_err(FX_E_ARG, "search: stale selector: it is a snapshot of %lld rows, the index now has %lld "
+                       "(rows were added or the index was reset since it was created)",
+                       (long long)sel->ntotal, (long long)h->ntotal);
+    DeviceGuard g(h->device);
+    {
+        const int rc = selector_counts(sel);
+        if (rc != FX_OK) return rc;
+    }
+    // nothing selected (or an empty index): every slot missing, no scan
+    if (h->ntotal == 0 || sel->rows == 0) return fill_missing(h, nq, k, D, I, out_mem);
+    return do_search(h, nq, q, q_dtype, q_mem, k, D, I, out_mem, sel);
 }
 
 // the counts of the last search (after a device-resident one: synchronises the
@@ -1729,6 +1934,7 @@ int fx_index_reset(FxIndex* h) {
         HIP_TRY(hipMemsetD32((hipDeviceptr_t)h->norms, 0x7f800000u, (size_t)h->cap_rows));
     }
     h->ntotal = 0;
+    ++h->epoch;
     h->img_rows = 0;
     h->mu_rows = 0;
     h->rg_nq = -1;  // the last range search's result goes with the rows

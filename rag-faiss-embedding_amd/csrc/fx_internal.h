@@ -1,5 +1,5 @@
 // fx_internal.h -- shared between the HIP translation units (fx_kernels.hip,
-// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip) and the host C ABI
+// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip) and the host C ABI
 // (fx_index.cpp): tiling constants, kernel parameter blocks, the launchers'
 // prototypes and their host-side helpers.  Not part of the public ABI
 // (include/fx_index.h).
@@ -257,11 +257,12 @@ int scan_v5_qt(int st_dt, int row_bytes);  // its queries per workgroup for thes
 hipError_t launch_scan_v5(int st_dt, int metric, const ScanParams& p, hipStream_t s);
 constexpr int V5_TR = 64;
 // both fallback launches, always enqueued; they read the flagged count at
-// n_flag[0] (list at n_flag + 1) and do nothing when it is 0
+// n_flag[0] (list at n_flag + 1) and do nothing when it is 0.  row_mask
+// non-null (a filtered search): only rows whose mask bit is set are ranked
 hipError_t launch_exact_fallback(int st_dt, int metric, const char* codes, int row_bytes, int kdim,
                                  int64_t ntotal, const float* qf32, const int* n_flag, int k,
                                  int64_t id_offset, float* cand_d, int* cand_i, float* D, int64_t* I,
-                                 hipStream_t s);
+                                 hipStream_t s, const uint32_t* row_mask = nullptr);
 hipError_t launch_merge_shards(int metric, int nshards, int64_t nq, int k, const float* D_in,
                                const int64_t* I_in, float* D_out, int64_t* I_out, hipStream_t s);
 // k > FX_BIG_K (fx_hugek.hip): exact key of every (query, row) pair, a radix
@@ -320,6 +321,33 @@ struct RangeFinish {
 };
 hipError_t range_sort_temp_bytes(int64_t n, int64_t nq, size_t* bytes);
 hipError_t launch_range_finish(const RangeFinish& f, hipStream_t s);
+// filtered search (fx_select.hip).  A selector's device image: the row mask
+// (bit r & 31 of word r >> 5 set: local row r is selected; 4 words per 128-row
+// tile, zero past ntotal), the ascending list of the tiles with a selected
+// row, and their counts.
+struct SelCounts {
+    long long rows;  // selected rows
+    int tiles;       // live tiles (entries of the tile list)
+    int pad;
+};
+inline int64_t sel_mask_words(int64_t ntotal) { return (ntotal + TILE_R - 1) / TILE_R * (TILE_R / 32); }
+// mask builders over rows [0, ntotal) (ids = row + id_offset); invert != 0:
+// the complement within those rows.  Each writes every word of the mask.
+//   bitmap: id i is a member iff bits[i >> 3] & (1 << (i & 7)), i < 8 nbytes
+//   ids:    n int64 ids (duplicates and ids outside the index ignored)
+//   range:  local rows [lo, hi), 0 <= lo <= hi <= ntotal
+hipError_t launch_sel_bitmap(const uint8_t* bits, int64_t nbytes, int64_t id_offset, int64_t ntotal, int invert,
+                             uint32_t* mask, hipStream_t s);
+hipError_t launch_sel_ids(const int64_t* ids, int64_t n, int64_t id_offset, int64_t ntotal, int invert,
+                          uint32_t* mask, hipStream_t s);
+hipError_t launch_sel_range(int64_t lo, int64_t hi, int64_t ntotal, int invert, uint32_t* mask, hipStream_t s);
+// tiles[0, cnt->tiles) <- the tiles of the mask with a set bit, ascending; cnt <- the counts
+hipError_t launch_sel_tiles(const uint32_t* mask, int64_t ntotal, int* tiles, SelCounts* cnt, hipStream_t s);
+// k_scan_topk over the selector's live tiles and selected rows only (p as
+// launch_range_scan's: the stored rows, qt = TILE_Q, tr = TILE_R); the same
+// [qtile][split][TILE_Q][KP] candidate lists, every split's written
+hipError_t launch_scan_sel(int st_dt, int metric, const ScanParams& p, const uint32_t* mask, const int* tiles,
+                           const SelCounts* cnt, hipStream_t s);
 // fp32 code rows [r0, r1) -> their F32S scan image (same row stride)
 // (centred by mu when non-null), with the image rows' |v|^2 -> cnorms and their
 // maximum -> cmax_bits (atomicMax)

@@ -1167,14 +1167,16 @@ __global__ __launch_bounds__(BT_THREADS) void k_refine_big(RefineParams p) {
 // uncertified count n_flag[0] (list at n_flag + 1) and exit at once when it
 // is 0, so a device-resident search never waits for the host.
 // k_fb_scan: work item = (flagged query f, corpus split); exact fp64 key of
-// every row of the split, block top-k -> cd/ci[item][k].
+// every row of the split (with a row mask: every selected row), block top-k
+// -> cd/ci[item][k].
 // k_fb_merge: per flagged query, top-k of its splits' lists -> D / I.
 // ---------------------------------------------------------------------------
 template <int DT, int METRIC>
 __global__ __launch_bounds__(BT_THREADS) void k_fb_scan(const char* __restrict__ codes, int row_bytes, int kdim,
                                                         int64_t ntotal, const float* __restrict__ qf32,
                                                         const int* __restrict__ n_flag, int k,
-                                                        float* __restrict__ cd, int* __restrict__ ci) {
+                                                        float* __restrict__ cd, int* __restrict__ ci,
+                                                        const uint32_t* __restrict__ row_mask) {
     __shared__ float sd[BT_MAXB];
     __shared__ int si[BT_MAXB];
     __shared__ BtState<int> st;
@@ -1190,7 +1192,8 @@ __global__ __launch_bounds__(BT_THREADS) void k_fb_scan(const char* __restrict__
         bt_init(&st);
         for (int64_t base = r0; base < r1; base += BT_THREADS) {
             const int64_t row = base + threadIdx.x;
-            const bool valid = row < r1;
+            // (a filtered search: the selector's row mask, fx_select.hip)
+            const bool valid = row < r1 && (!row_mask || ((row_mask[row >> 5] >> (row & 31)) & 1u) != 0);
             float key = FX_INF;
             if (valid) {
                 const double v = exact_partial<DT, METRIC>(xq, codes + row * row_bytes, row_bytes, 0, 1);
@@ -1467,10 +1470,10 @@ hipError_t launch_refine(int st_dt, int metric, const RefineParams& p, hipStream
 
 hipError_t launch_exact_fallback(int st_dt, int metric, const char* codes, int row_bytes, int kdim, int64_t ntotal,
                                  const float* qf32, const int* n_flag, int k, int64_t id_offset, float* cand_d,
-                                 int* cand_i, float* D, int64_t* I, hipStream_t s) {
+                                 int* cand_i, float* D, int64_t* I, hipStream_t s, const uint32_t* row_mask) {
     hipError_t e = dispatch_dt_metric<DT_STORED>(st_dt, metric, [&](auto dt, auto mt) {
         hipLaunchKernelGGL((k_fb_scan<dt(), mt()>), dim3(FB_SCAN_GRID), dim3(BT_THREADS), 0, s, codes, row_bytes, kdim,
-                           ntotal, qf32, n_flag, k, cand_d, cand_i);
+                           ntotal, qf32, n_flag, k, cand_d, cand_i, row_mask);
         return hipGetLastError();
     });
     if (e != hipSuccess) return e;

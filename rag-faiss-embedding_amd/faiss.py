@@ -9,6 +9,10 @@ as faiss``:
   ``.metric_type``, ``.is_trained``, ``.add(x)``, ``.search(x, k) -> (D, I)``,
   ``.range_search(x, radius) -> (lims, D, I)``, ``.reset()``,
   ``.reconstruct_n(i0, n)``;
+* filtered search, ``index.search(x, k, params=SearchParameters(sel=...))``
+  with ``IDSelectorRange``, ``IDSelectorArray``, ``IDSelectorBatch``,
+  ``IDSelectorBitmap`` and ``IDSelectorNot``: only the selected ids are ranked
+  (exactly: the scan itself skips the other rows);
 * ``write_index(index, path)`` / ``read_index(path)`` on the IxF2 format.
 
 Inputs may be numpy arrays (as in the reference: host fp32, results returned
@@ -23,6 +27,7 @@ SWIG wrapper's ``assert d == self.d``); library failures raise
 from __future__ import annotations
 
 import ctypes
+import weakref
 from typing import Optional, Tuple
 
 import numpy as np
@@ -59,8 +64,186 @@ def _tensor_dtype(x) -> int:
     return m[x.dtype]
 
 
+# ---------------------------------------------------------------------------
+# faiss IDSelector / SearchParameters (include/fx_index.h "filtered search")
+# ---------------------------------------------------------------------------
+class IDSelector:
+    """A set of ids a search is restricted to.  Ids are the ids ``search``
+    returns (row + the index's id offset).  The device image a search needs
+    (``FxSelector``: row mask + live tiles) is built on first use and cached
+    per index for the index's current ``ntotal`` and id offset; after ``add``
+    / ``reset`` it is rebuilt transparently."""
+
+    _kind = -1
+
+    def _spec(self):
+        """(kind, data, n, invert): data a numpy array, a device tensor or None."""
+        raise NotImplementedError
+
+    def _handle(self, index: "_FlatIndex") -> ctypes.c_void_p:
+        # id(index) -> (key, handle, library, weak reference to the index): the
+        # handle goes when the index does, when it is stale, or with self
+        cache = self.__dict__.setdefault("_built", {})
+        key = (index.ntotal, index._id_offset, index._resets)
+        hit = cache.get(id(index))
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        if hit is not None:
+            del cache[id(index)]
+            hit[2].fx_selector_free(hit[1])
+        kind, data, n, invert = self._spec()
+        h = ctypes.c_void_p()
+        if _is_device_tensor(data):
+            assert data.device.index == index.device, \
+                f"selector data on cuda:{data.device.index}, index on cuda:{index.device}"
+            ptr, mem = ctypes.c_void_p(data.data_ptr()), _lib.MEM_DEVICE
+        else:
+            ptr, mem = (ctypes.c_void_p(data.ctypes.data) if data is not None and data.size else None), _lib.MEM_HOST
+        index._check(index._lib.fx_selector_create(index._h, kind, ptr, int(n), mem, 1 if invert else 0,
+                                                   ctypes.byref(h)))
+        so, iid = index._lib, id(index)
+
+        def index_gone(_ref, cache=cache, iid=iid):
+            old = cache.pop(iid, None)
+            if old is not None and old[2] is not None:
+                old[2].fx_selector_free(old[1])  # (valid after the index was freed)
+
+        cache[iid] = (key, h, so, weakref.ref(index, index_gone))
+        return h
+
+    def stats(self, index: "_FlatIndex") -> dict:
+        """Of this selector on ``index``: selected ``rows`` and live 128-row
+        ``tiles`` (the tiles the filtered scan visits)."""
+        index._bind_stream(_is_device_tensor(self._spec()[1]))
+        r, t = ctypes.c_int64(0), ctypes.c_int64(0)
+        index._check(index._lib.fx_selector_stats(self._handle(index), ctypes.byref(r), ctypes.byref(t)))
+        return {"rows": r.value, "tiles": t.value}
+
+    def __del__(self):
+        try:  # (at interpreter shutdown the library or the cache may be gone already)
+            built = self.__dict__.pop("_built", None) or {}
+            for _, h, so, _ref in list(built.values()):
+                if so is not None and h is not None and h.value:
+                    so.fx_selector_free(h)
+            built.clear()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def _id_array(ids):
+    if _is_device_tensor(ids):
+        t = _torch()
+        assert ids.dtype == t.int64, "device ids must be an int64 tensor"
+        return ids.contiguous().view(-1)
+    return np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int64)
+
+
+class IDSelectorRange(IDSelector):
+    """``faiss.IDSelectorRange(imin, imax)``: ids with imin <= id < imax."""
+
+    _kind = 2
+
+    def __init__(self, imin: int, imax: int, assume_sorted: bool = False):
+        self.imin, self.imax = int(imin), int(imax)
+        if self.imax < self.imin:
+            raise AssertionError("IDSelectorRange: imax < imin")
+
+    def _spec(self):
+        return self._kind, np.array([self.imin, self.imax], dtype=np.int64), 2, False
+
+
+class IDSelectorArray(IDSelector):
+    """``faiss.IDSelectorArray(ids)``: the listed ids (duplicates and ids
+    outside the index are ignored).  ``ids``: anything numpy converts to
+    int64, or an int64 tensor on the index's GPU (then read stream-ordered)."""
+
+    _kind = 1
+
+    def __init__(self, *args):
+        # faiss spells it (n, ids) in C++ and (ids) in Python
+        ids = args[-1]
+        self.ids = _id_array(ids)
+        if len(args) == 2:
+            self.ids = self.ids[:int(args[0])]
+
+    def _spec(self):
+        n = int(self.ids.numel()) if _is_device_tensor(self.ids) else int(self.ids.size)
+        return self._kind, self.ids, n, False
+
+
+class IDSelectorBatch(IDSelectorArray):
+    """``faiss.IDSelectorBatch(ids)``: the same set as ``IDSelectorArray``
+    (faiss's hash-set variant; here both build the same row mask)."""
+
+
+class IDSelectorBitmap(IDSelector):
+    """``faiss.IDSelectorBitmap(bitmap)`` / ``(n, bitmap)``: id i is selected
+    iff ``bitmap[i >> 3] & (1 << (i & 7))``; ids past the bitmap's 8 n bits are
+    not.  ``bitmap``: uint8 numpy array or uint8 tensor on the index's GPU."""
+
+    _kind = 0
+
+    def __init__(self, *args):
+        bitmap = args[-1]
+        if _is_device_tensor(bitmap):
+            assert bitmap.dtype == _torch().uint8, "a device bitmap must be a uint8 tensor"
+            self.bitmap = bitmap.contiguous().view(-1)
+            size = int(self.bitmap.numel())
+        else:
+            self.bitmap = np.ascontiguousarray(np.asarray(bitmap).reshape(-1), dtype=np.uint8)
+            size = int(self.bitmap.size)
+        self.n = size
+        if len(args) == 2:
+            self.n = int(args[0])
+            assert 0 <= self.n <= size, "IDSelectorBitmap: n exceeds the bitmap"
+
+    def _spec(self):
+        return self._kind, self.bitmap, self.n, False
+
+
+class IDSelectorNot(IDSelector):
+    """``faiss.IDSelectorNot(sel)``: the ids of the index ``sel`` does not
+    select.  ``IDSelectorNot(IDSelectorNot(s))`` is ``s`` itself."""
+
+    def __new__(cls, sel):
+        if isinstance(sel, IDSelectorNot):
+            return sel.sel
+        return super().__new__(cls)
+
+    def __init__(self, sel):
+        if not isinstance(sel, IDSelector):
+            raise TypeError("IDSelectorNot takes an IDSelector (And / Or / XOr are not supported)")
+        self.sel = sel
+
+    def _spec(self):
+        kind, data, n, invert = self.sel._spec()
+        return kind, data, n, not invert
+
+
+class SearchParameters:
+    """``faiss.SearchParameters(sel=None)``: per-search parameters; ``sel`` an
+    ``IDSelector`` restricting the search, None for all rows."""
+
+    def __init__(self, sel: Optional[IDSelector] = None):
+        if sel is not None and not isinstance(sel, IDSelector):
+            raise TypeError("sel must be an IDSelector")
+        self.sel = sel
+
+
+def _selector_of(params) -> Optional[IDSelector]:
+    if params is None:
+        return None
+    sel = getattr(params, "sel", None)
+    if sel is not None and not isinstance(sel, IDSelector):
+        raise TypeError("params.sel must be an IDSelector of this module")
+    return sel
+
+
 class _FlatIndex:
     """Common implementation of IndexFlatL2 / IndexFlatIP."""
+
+    _id_offset = 0
+    _resets = 0  # reset() calls: with ntotal and the id offset, what a built selector is a snapshot of
 
     metric_type: int = METRIC_L2
     _lib = lib  # the ctypes build this index lives in (the diagnostic build: diag.py)
@@ -123,14 +306,19 @@ class _FlatIndex:
         self._check(self._lib.fx_index_add(self._h, x.shape[0], x.ctypes.data_as(ctypes.c_void_p), _lib.F32,
                                            _lib.MEM_HOST))
 
-    def search(self, x, k: int, *, D=None, I=None) -> Tuple:
+    def search(self, x, k: int, *, params=None, D=None, I=None) -> Tuple:
         """``IndexFlat.search`` (faiss_store.py:64): k nearest rows of every
         query row.  Returns ``(D, I)`` shaped ``(nq, k)``.  Any k, as faiss:
         k <= ``MAX_K`` runs the fused scan, larger k the exact sort path;
-        slots past ntotal hold I = -1, D = +-FLT_MAX."""
+        slots past ntotal hold I = -1, D = +-FLT_MAX.
+
+        ``params=SearchParameters(sel=IDSelector...)`` ranks only the selected
+        ids (k <= ``MAX_K``); with fewer than k of them the remaining slots are
+        missing ones.  Without a selector the call is the unfiltered one."""
         k = int(k)
         if k <= 0:
             raise AssertionError("k must be positive")
+        sel = None if params is None else _selector_of(params)
         if _is_device_tensor(x):
             t = _torch()
             assert x.dim() == 2 and x.shape[1] == self.d, "dimension mismatch"
@@ -147,6 +335,12 @@ class _FlatIndex:
                 assert a.dtype == dt and tuple(a.shape) == (nq, k) and a.is_contiguous(), \
                     f"{name} must be a contiguous {dt} tensor of shape ({nq}, {k})"
             self._bind_stream(True)
+            if sel is not None:
+                self._check(self._lib.fx_index_search_sel(self._h, sel._handle(self), nq, ctypes.c_void_p(x.data_ptr()),
+                                                          _tensor_dtype(x), _lib.MEM_DEVICE, k,
+                                                          ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()),
+                                                          _lib.MEM_DEVICE))
+                return D, I
             self._check(self._lib.fx_index_search(self._h, nq, ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x),
                                                   _lib.MEM_DEVICE, k, ctypes.c_void_p(D.data_ptr()),
                                                   ctypes.c_void_p(I.data_ptr()), _lib.MEM_DEVICE))
@@ -161,13 +355,19 @@ class _FlatIndex:
             assert isinstance(a, np.ndarray) and a.dtype == dt and a.shape == (nq, k) and \
                 a.flags.c_contiguous and a.flags.writeable, \
                 f"{name} must be a writeable C-contiguous {np.dtype(dt).name} array of shape ({nq}, {k})"
+        if sel is not None:
+            # (a selector built from a device tensor is read on the stream that tensor was made on)
+            self._bind_stream(_is_device_tensor(sel._spec()[1]))
+            self._check(self._lib.fx_index_search_sel(self._h, sel._handle(self), nq, x.ctypes.data, _lib.F32,
+                                                      _lib.MEM_HOST, k, Dh.ctypes.data, Ih.ctypes.data, _lib.MEM_HOST))
+            return Dh, Ih
         self._bind_stream(False)
         # (raw addresses: .ctypes.data is an int, much cheaper per call than data_as)
         self._check(self._lib.fx_index_search(self._h, nq, x.ctypes.data, _lib.F32, _lib.MEM_HOST, k,
                                               Dh.ctypes.data, Ih.ctypes.data, _lib.MEM_HOST))
         return Dh, Ih
 
-    def range_search(self, x, radius: float) -> Tuple:
+    def range_search(self, x, radius: float, *, params=None) -> Tuple:
         """``IndexFlat.range_search``: every row within ``radius`` of each
         query row -- ``D < radius`` (L2 index) or ``x.y > radius`` (IP), both
         strict, decided on the exact distance.  Returns ``(lims, D, I)``:
@@ -175,6 +375,9 @@ class _FlatIndex:
         ordered by ascending row id.  numpy in -> numpy out (``lims`` uint64,
         as faiss); a device tensor in -> D and I device tensors and ``lims``
         an int64 tensor on the same device."""
+        if _selector_of(params) is not None:
+            raise NotImplementedError("range_search with an IDSelector is not supported: filtered search is "
+                                      "search(x, k, params=...) only")
         radius = float(radius)
         dev_in = _is_device_tensor(x)
         if dev_in:
@@ -243,6 +446,7 @@ class _FlatIndex:
 
     def reset(self) -> None:
         self._check(self._lib.fx_index_reset(self._h))
+        self._resets += 1
 
     def reserve(self, n: int) -> None:
         self._check(self._lib.fx_index_reserve(self._h, int(n)))
@@ -255,6 +459,7 @@ class _FlatIndex:
 
     def set_id_offset(self, offset: int) -> None:
         self._check(self._lib.fx_index_set_id_offset(self._h, int(offset)))
+        self._id_offset = int(offset)  # (built selectors are keyed on it: ids are row + offset)
 
     def set_option(self, name: str, value: int) -> None:
         """Per-index tuning / diagnostic option (include/fx_index.h

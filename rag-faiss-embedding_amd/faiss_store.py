@@ -64,16 +64,31 @@ class FAISSVectorStore:
         self.index.add(rows)
         logger.info("add: %d ids -> ntotal %d", len(ids), self.index.ntotal)
 
-    def search(self, query_vector, k: int = 5) -> Tuple[np.ndarray, List[int]]:
+    def _rows_selector(self, allowed_ids):
+        """Document ids -> the index rows that carry them (every row of an id
+        that occurs more than once in ``doc_ids``; unknown ids select nothing)
+        as ``SearchParameters`` with an ``IDSelectorBatch``."""
+        allowed = set(int(a) for a in allowed_ids)
+        rows = [r for r, doc in enumerate(self.doc_ids) if doc in allowed]
+        return _fx.SearchParameters(sel=_fx.IDSelectorBatch(np.asarray(rows, dtype=np.int64)))
+
+    def search(self, query_vector, k: int = 5, allowed_ids=None) -> Tuple[np.ndarray, List[int]]:
         """faiss_store.py:49-81: one query; index rows map to document ids,
         -1 and rows past the id list are dropped; on any error the result is
         ``(np.array([]), [])``.  Any k, as faiss (k > ``FX_MAX_K`` = 1024
-        takes the index's exact sort path)."""
+        takes the index's exact sort path).
+
+        ``allowed_ids`` (document ids; extension): only those documents are
+        ranked -- the index's filtered search over their rows (k <=
+        ``FX_MAX_K``), so a narrow filter still returns its k nearest."""
         try:
             q = query_vector
             if isinstance(q, list):
                 q = np.array(q, dtype=np.float32)
-            dist, rows = self.index.search(q.reshape(1, -1), k)
+            if allowed_ids is None:
+                dist, rows = self.index.search(q.reshape(1, -1), k)
+            else:
+                dist, rows = self.index.search(q.reshape(1, -1), k, params=self._rows_selector(allowed_ids))
             if not isinstance(dist, np.ndarray):  # device tensors -> host
                 dist, rows = dist.cpu().numpy(), rows.cpu().numpy()
             n_ids = len(self.doc_ids)

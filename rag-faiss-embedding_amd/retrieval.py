@@ -79,16 +79,31 @@ def _to_numpy(x) -> np.ndarray:
     return np.asarray(x)
 
 
+def selector_for_documents(doc_ids: Sequence[int], allowed_ids: Iterable[int]):
+    """``faiss.SearchParameters`` selecting the index rows whose document id is
+    in ``allowed_ids`` (``doc_ids`` is the row -> document id mapping; an id
+    held by several rows selects them all, an unknown id none)."""
+    from . import faiss as fx
+    allowed = np.fromiter((int(a) for a in allowed_ids), dtype=np.int64)
+    rows = np.flatnonzero(np.isin(np.asarray(doc_ids, dtype=np.int64), allowed))
+    return fx.SearchParameters(sel=fx.IDSelectorBatch(rows.astype(np.int64)))
+
+
 def search_similar_documents(index, doc_ids: Sequence[int], store: DocumentStore, query_embeddings,
-                             k: int = 5) -> List[List[Dict]]:
+                             k: int = 5, allowed_ids: Optional[Iterable[int]] = None) -> List[List[Dict]]:
     """Batched ``RAGDatabaseManager.search_similar_documents``
     (rag_datastore_manager.py:211-238): for every query row, the documents
     of its k nearest index rows, nearest first, each with ``distance`` (the
     squared L2 distance the index returned).  ``doc_ids`` is the row -> doc
-    id mapping (faiss_index.bin.mapping).  Errors are logged and give empty
-    lists, as the reference's blanket ``except`` does."""
+    id mapping (faiss_index.bin.mapping).  ``allowed_ids`` (document ids):
+    only those documents are ranked, by the index's filtered search.  Errors
+    are logged and give empty lists, as the reference's blanket ``except``
+    does."""
     try:
-        D, I = index.search(query_embeddings, int(k))
+        if allowed_ids is None:
+            D, I = index.search(query_embeddings, int(k))
+        else:
+            D, I = index.search(query_embeddings, int(k), params=selector_for_documents(doc_ids, allowed_ids))
         D, I = _to_numpy(D), _to_numpy(I)
         ids = np.asarray(doc_ids, dtype=np.int64)
         valid = (I >= 0) & (I < len(ids))
@@ -214,10 +229,12 @@ class RetrievalEngine:
             return self.vectorizer.generate_embeddings_device(texts)
         return np.asarray(self.vectorizer.generate_embeddings(texts), dtype=np.float32)
 
-    def search(self, texts: List[str], k: int = 5) -> List[List[Dict]]:
+    def search(self, texts: List[str], k: int = 5, allowed_ids: Optional[Iterable[int]] = None) -> List[List[Dict]]:
+        """``allowed_ids``: rank only these document ids (filtered search)."""
         if not texts:
             return []
-        return search_similar_documents(self.index, self.doc_ids, self.store, self.embed(texts), k)
+        return search_similar_documents(self.index, self.doc_ids, self.store, self.embed(texts), k,
+                                        allowed_ids=allowed_ids)
 
     def search_within(self, texts: List[str], *, max_distance: Optional[float] = None,
                       min_score: Optional[float] = None) -> List[List[Dict]]:

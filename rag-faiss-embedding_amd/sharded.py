@@ -118,8 +118,13 @@ class ShardedIndexFlatL2:
             return as_np(Dm), as_np(Im)
         return Dm, Im
 
-    def search(self, xq, k: int):
+    def search(self, xq, k: int, params=None):
         """Global top-k: local scan -> exchange (one all_gather + merge).
+
+        ``params`` (``faiss.SearchParameters`` with an ``IDSelector``) goes to
+        every rank's local search: selector ids are global ids, and a rank's
+        index carries its block's id offset, so each rank selects its own part
+        of the set.  None: the unfiltered search, called exactly as before.
 
         Host queries under RCCL (the reference's numpy call form,
         faiss_store.py:61-64): the queries go to this rank's GPU once, the
@@ -130,24 +135,25 @@ class ShardedIndexFlatL2:
         A host-input search fails on EVERY rank when one rank's local search
         failed or dropped corrupted candidate ids (one flag all_reduce before
         the exchange), so the ranks' collectives stay in step."""
+        kw = {} if params is None else {"params": params}
         if self.world == 1:
-            return self.local.search(xq, k)
+            return self.local.search(xq, k, **kw)
         host_in = not (isinstance(xq, torch.Tensor) and xq.is_cuda)
         if host_in and dist.get_backend(self.group) == "nccl":
-            return self.search_host_on_device(xq, k)
+            return self.search_host_on_device(xq, k, params)
         if not host_in:  # device lists: the caller reads the integrity count (INTEGRATION.md)
-            D, I = self.local.search(xq, k)
+            D, I = self.local.search(xq, k, **kw)
             return self.exchange(D, I, k)
         D = I = None
         why = None
         try:
-            D, I = self.local.search(xq, k)  # host output: raises FX_E_INTEGRITY itself
+            D, I = self.local.search(xq, k, **kw)  # host output: raises FX_E_INTEGRITY itself
         except Exception as e:  # noqa: BLE001 -- re-raised on every rank below
             why = f"{type(e).__name__}: {e}"
         self._agree(why, torch.zeros(1))
         return self.exchange(D, I, k)
 
-    def search_host_on_device(self, xq, k: int):
+    def search_host_on_device(self, xq, k: int, params=None):
         """search() of host queries under RCCL: H2D of the queries, local
         scan, all_gather and merge on the exchange device, ONE D2H of the
         merged lists (numpy in -> numpy out, a host tensor -> host tensors)."""
@@ -157,7 +163,7 @@ class ShardedIndexFlatL2:
         D = I = None
         why = None
         try:
-            D, I = self.local.search(xt.to(dev), k)
+            D, I = self.local.search(xt.to(dev), k, **({} if params is None else {"params": params}))
             why = self._integrity_problem()
         except Exception as e:  # noqa: BLE001 -- re-raised on every rank below
             why = f"{type(e).__name__}: {e}"
