@@ -19,6 +19,9 @@
  *   index.search(x, k,    (a query restricted to     faiss_Index_search_with_     fx_index_search_sel
  *     params=...)          one document set; see      params                      + fx_selector_create
  *                          "filtered search" below)
+ *   index.remove_ids(sel) (documents re-crawled,     faiss_Index_remove_ids       fx_index_remove_ids
+ *                          edited or deleted; see                                  + fx_selector_create
+ *                          "row removal" below)
  *   index.ntotal          faiss_store.py:53          faiss_Index_ntotal           fx_index_ntotal
  *   (re)IndexFlatL2(d)    faiss_store.py:126         faiss_Index_reset            fx_index_reset
  *   faiss.write_index     faiss_store.py:91,         faiss_write_index_fname      fx_index_write
@@ -121,7 +124,10 @@ int fx_index_set_stream(FxIndex* index, void* stream);
  * "host_spin" 0/1, "range_cap" 0 (= 1,048,576) or 1 .. 2^30 (entries, 8 B
  * each, the range_search candidate buffer starts with; a call whose scan
  * emits more grows it to the emitted count and scans a second time; setting
- * the option drops a grown buffer).  None changes results, only
+ * the option drops a grown buffer), "remove_stage" 0 (= 256 MiB) or row
+ * bytes .. 2^32 (bytes of the staging buffer fx_index_remove_ids gathers
+ * overlapping chunks of rows into; a smaller one means more, smaller
+ * chunks).  None changes results, only
  * speed.  Unknown name or out-of-range value: FX_E_ARG.  (The diagnostic
  * build libfx_index_diag.so adds test hooks -- "force_fallback",
  * "scan_dbg" -- that the product library does not have.) */
@@ -200,8 +206,8 @@ int fx_index_last_range_stats(FxIndex* index, int64_t* candidates, int* passes);
  * [0, ntotal) at creation: it owns a device row mask (one bit per row) and the
  * ascending list of the 128-row tiles that hold a selected row; the filtered
  * scan visits those tiles only, and rows that are not selected never become
- * candidates.  After rows are added or the index is reset the snapshot no
- * longer describes the index: create a new selector. */
+ * candidates.  After rows are added or removed or the index is reset the
+ * snapshot no longer describes the index: create a new selector. */
 typedef struct FxSelector FxSelector;
 enum { FX_SEL_BITMAP = 0, FX_SEL_IDS = 1, FX_SEL_RANGE = 2 };
 
@@ -238,6 +244,30 @@ int fx_selector_stats(const FxSelector* sel, int64_t* rows, int64_t* tiles);
  * calls report a filtered search like any other. */
 int fx_index_search_sel(FxIndex* index, const FxSelector* sel, int64_t nq, const void* q, int q_dtype, int q_mem,
                         int k, float* D, int64_t* I, int out_mem);
+
+/* ---- row removal: faiss IndexFlatCodes::remove_ids -----------------------
+ *
+ * IndexFlatCodes::remove_ids (faiss_Index_remove_ids): remove the selector's
+ * rows.  Any selector of fx_selector_create (bitmap, ids, range, inverted)
+ * that is a current snapshot of this index; one created on another index or
+ * a stale one: FX_E_ARG, as fx_index_search_sel.  The kept rows keep their
+ * relative order and are renumbered densely (local row r again has id
+ * r + id_offset), ntotal drops by the count and *n_removed receives it.  The
+ * rows are compacted where they lie (no second copy of the corpus: a staging
+ * buffer of at most "remove_stage" bytes, 4 bytes per staged row for the
+ * norms, and one word per 32 rows of prefix data).  Blocks.  Nothing
+ * selected: FX_OK, *n_removed = 0, nothing changes and the selector stays
+ * valid.  Otherwise every selector from before the call, the one passed in
+ * included, is stale afterwards (also once later adds restore the old
+ * ntotal), and the stored range-search result is dropped. */
+int fx_index_remove_ids(FxIndex* index, const FxSelector* sel, int64_t* n_removed);
+/* The plan of the last removal that removed a row (no faiss counterpart; for
+ * benchmarks): the first removed row, the kept rows above it that one launch
+ * moved in place (read once, written once) and those gathered into staging
+ * and copied into place (read and written twice), and the chunks launched.
+ * All 0 before the first removal. */
+int fx_index_last_remove_stats(FxIndex* index, int64_t* first, int64_t* direct_rows, int64_t* staged_rows,
+                               int64_t* chunks);
 
 /* Number of queries of the last search whose top-k could not be certified
  * from the scan's candidate margin and were re-scanned with a wide candidate

@@ -61,6 +61,9 @@ SIGNATURES = {
     "fx_selector_free": (None, [_vp]),
     "fx_selector_stats": (_i, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "fx_index_search_sel": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _vp, _vp, _i]),
+    "fx_index_remove_ids": (_i, [_vp, _vp, ctypes.POINTER(_i64)]),
+    "fx_index_last_remove_stats": (_i, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                        ctypes.POINTER(_i64)]),
     "fx_index_last_fallbacks": (_i, [_vp, ctypes.POINTER(_i64)]),
     "fx_index_last_scan_plan": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "fx_index_last_exact_fallbacks": (_i, [_vp, ctypes.POINTER(_i64)]),

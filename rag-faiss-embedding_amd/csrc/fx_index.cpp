@@ -83,6 +83,9 @@ inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 // range_cap says otherwise (8 B each, plus 24 B per candidate actually found
 // for the exact distances, the sort and the result), and the option's limit
 constexpr int RANGE_CAP_DEFAULT = 1 << 20, RANGE_CAP_MAX = 1 << 30;
+// remove_ids' staging buffer in bytes unless the option remove_stage says
+// otherwise (one row .. REMOVE_STAGE_MAX)
+constexpr int64_t REMOVE_STAGE_DEFAULT = 256ll << 20, REMOVE_STAGE_MAX = 1ll << 32;
 
 // Per-index tuning options.  Initial values come from the FX_* environment
 // variables, read ONCE when the index is created (never on the search path);
@@ -128,6 +131,8 @@ struct Options {
                              // 1: (d) 1.8x slower -- every block of a split writing one line each tile)
     int range_cap = 0;       // FX_RANGE_CAP: entries the range_search candidate buffer starts with (0: the
                              // default RANGE_CAP_DEFAULT; a call that finds more grows it and scans again)
+    int64_t remove_stage = 0;  // FX_REMOVE_STAGE: bytes of remove_ids' staging buffer (0: REMOVE_STAGE_DEFAULT;
+                               // row_bytes .. REMOVE_STAGE_MAX, checked by fx_index_set_option / at use)
     int host_spin = 1;       // FX_HOST_SPIN: a host-output search waits for its results by polling the
                              // stream (1) instead of a blocking hipStreamSynchronize (0)
 #ifdef FX_DIAG
@@ -167,6 +172,8 @@ struct Options {
         num("FX_REFINE_WAVES", refine_waves);
         num("FX_RANGE_CAP", range_cap);
         if (range_cap < 0 || range_cap > RANGE_CAP_MAX) range_cap = 0;
+        if (const char* e = getenv("FX_REMOVE_STAGE"); e && *e) remove_stage = atoll(e);
+        if (remove_stage < 0 || remove_stage > REMOVE_STAGE_MAX) remove_stage = 0;
         if (refine_waves != 4 && refine_waves != 8 && refine_waves != 16) refine_waves = REFINE_WG_WAVES;
         (void)str;
 #ifdef FX_DIAG
@@ -341,6 +348,10 @@ struct FxIndex {
     int64_t rg_total = 0;     // its lims[nq]
     int64_t rg_cands = 0;     // pairs the MFMA scan emitted
     int rg_passes = 0;        // scan passes run (0: no scan was needed)
+    // remove_ids (fx_remove.hip): [prefix | gp | block sums | info | staged norms] (remove_rows)
+    DevBuf rm_ws;
+    // the last removal's plan: first removed row, rows moved in place / through staging, chunks launched
+    int64_t rm_stats[4] = {0, 0, 0, 0};
     DevBuf conv;  // k_scan_v5 convoy words (CONV_WORDS; zeroed once, then only hints)
     int last_plan[3] = {0, 0, 0};  // the last search's scan plan: tile rows (128 k_scan_v4, 64 k_scan_v5), qt, splits
     // profiling
@@ -348,7 +359,7 @@ struct FxIndex {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_scan, ev_merge;
     std::mutex mu;
 
-    uint64_t epoch = 0;  // bumped by reset: a selector (a snapshot of the rows) from before is stale
+    uint64_t epoch = 0;  // bumped by reset and by a removal: a selector (a snapshot of the rows) from before is stale
 
     hipStream_t stream() const { return user_stream ? user_stream : own_stream; }
 };
@@ -1329,6 +1340,162 @@ int selector_counts(const FxSelector* sel) {
     return FX_OK;
 }
 
+// ---- remove_ids (fx_remove.hip): the host's chunk plan ----------------------
+
+// Kept rows before row r, for the rows the plan asks about: any row (the
+// prefix and mask words on the host; only for a staging buffer smaller than
+// RM_GROUP_ROWS rows) or the multiples of RM_GROUP_ROWS, the first removed
+// row and ntotal (the device's gp words).
+struct KeptPrefix {
+    int64_t ntotal = 0, first = 0, kept = 0;
+    int64_t g = RM_GROUP_ROWS;  // the plan's boundary granule: RM_GROUP_ROWS (gp) or 1 (words + mask)
+    std::vector<unsigned> gp, words, mask;
+    int64_t at(int64_t r) const {
+        if (r >= ntotal) return kept;
+        if (r <= first) return r;  // no row below the first removed one is removed
+        if (g == 1) return (int64_t)words[r >> 5] + __builtin_popcount(~mask[r >> 5] & ((1u << (r & 31)) - 1u));
+        return gp[r / RM_GROUP_ROWS];
+    }
+};
+
+struct RemoveChunk {
+    int64_t s0, s1;  // source rows
+    int64_t d0, kept;  // its kept rows go to rows [d0, d0 + kept)
+    bool direct;     // d0 + kept <= s0: moved in place by one launch; else gathered into staging, then copied
+};
+
+// Ascending chunks of source rows from the first removed row to ntotal, cut at
+// multiples of P.g.  From s0 (kept rows before it: d0) the candidates are the
+// longest direct chunk (the largest boundary s1 with prefix(s1) <= s0) and the
+// longest staged one (prefix(s1) - d0 <= stage_rows); the direct one is taken
+// when it is at least half as long (a staged row moves twice), so small
+// shifts do not turn into many small launches.  Chunks without a kept row are
+// skipped.  false: a boundary step holds more kept rows than the staging
+// buffer (never: the caller picks g <= stage_rows).
+bool plan_remove(const KeptPrefix& P, int64_t stage_rows, std::vector<RemoveChunk>& out) {
+    const int64_t g = P.g, nt = P.ntotal;
+    const int64_t nb = (nt + g - 1) / g;  // boundary i is row min(nt, i g)
+    auto row = [&](int64_t i) { return std::min(nt, i * g); };
+    int64_t s0 = P.first;
+    while (s0 < nt) {
+        const int64_t d0 = P.at(s0);
+        const int64_t i0 = s0 / g + 1;  // the first boundary above s0
+        // the largest boundary in [i0, nb] where pred holds (pred: true up to some row, false after); i0 - 1: none
+        auto last = [&](auto pred) {
+            int64_t lo = i0 - 1, hi = nb;
+            while (lo < hi) {
+                const int64_t mid = lo + (hi - lo + 1) / 2;
+                if (pred(row(mid))) lo = mid;
+                else hi = mid - 1;
+            }
+            return lo;
+        };
+        const int64_t id = last([&](int64_t r) { return P.at(r) <= s0; });
+        const int64_t is = last([&](int64_t r) { return P.at(r) - d0 <= stage_rows; });
+        if (is < i0) return false;
+        const int64_t s1d = id >= i0 ? row(id) : s0, s1s = row(is);
+        const bool direct = s1d > s0 && (s1d - s0) * 2 >= s1s - s0;
+        const int64_t s1 = direct ? s1d : s1s;
+        const int64_t kept = P.at(s1) - d0;
+        if (kept > 0) out.push_back({s0, s1, d0, kept, direct});
+        s0 = s1;
+    }
+    return true;
+}
+
+// The compaction itself: the index's rows under sel's mask (sel->rows > 0 of
+// them removed), then the invariants of grow() / fx_index_reset on the freed
+// tail, the recomputed norm maximum and the scan image's bookkeeping.
+int remove_rows(FxIndex* h, const FxSelector* sel) {
+    hipStream_t s = h->stream();
+    const int64_t nt = h->ntotal, rb = h->row_bytes;
+    const int64_t nw = sel_mask_words(nt), ngp = rm_groups(nt), nblk = rm_prefix_blocks(nt);
+    int64_t stage_bytes = h->opt.remove_stage;
+    if (stage_bytes < rb || stage_bytes > REMOVE_STAGE_MAX) stage_bytes = REMOVE_STAGE_DEFAULT;
+    const int64_t stage_rows = std::min(std::max<int64_t>(stage_bytes / rb, 1), nt);
+    HIP_TRY(h->rm_ws.ensure((size_t)(nw + ngp + nblk + 4 + stage_rows) * 4));
+    unsigned* prefix = (unsigned*)h->rm_ws.p;
+    unsigned* gp = prefix + nw;
+    unsigned* bsum = gp + ngp;
+    unsigned* info = bsum + nblk;
+    float* nstage = (float*)(info + 4);
+    HIP_TRY(launch_keep_prefix(sel->mask, nt, prefix, gp, bsum, info, s));
+    unsigned hinfo[2] = {0u, 0u};
+    HIP_TRY(hipMemcpyAsync(hinfo, info, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    KeptPrefix P;
+    P.ntotal = nt;
+    P.first = hinfo[0];
+    P.kept = hinfo[1];
+    if (P.first >= nt || P.kept != nt - sel->rows)
+        return set_err(FX_E_INTEGRITY, "remove_ids: the mask's scan gives first removed row %lld, %lld kept of %lld rows; "
+                       "the selector counted %lld selected", (long long)P.first, (long long)P.kept, (long long)nt,
+                       (long long)sel->rows);
+    P.g = stage_rows < std::min<int64_t>(RM_GROUP_ROWS, nt) ? 1 : RM_GROUP_ROWS;
+    if (P.g == 1) {
+        P.words.resize((size_t)nw);
+        P.mask.resize((size_t)nw);
+        HIP_TRY(hipMemcpyAsync(P.words.data(), prefix, (size_t)nw * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(P.mask.data(), sel->mask, (size_t)nw * 4, hipMemcpyDeviceToHost, s));
+    } else {
+        P.gp.resize((size_t)ngp);
+        HIP_TRY(hipMemcpyAsync(P.gp.data(), gp, (size_t)ngp * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<RemoveChunk> plan;
+    if (!plan_remove(P, stage_rows, plan)) return set_err(FX_E_INTEGRITY, "remove_ids: no chunk plan within the staging buffer");
+    int64_t staged_max = 0;
+    for (const RemoveChunk& c : plan)
+        if (!c.direct) staged_max = std::max(staged_max, c.kept);
+    if (staged_max > stage_rows) return set_err(FX_E_INTEGRITY, "remove_ids: a staged chunk exceeds the staging buffer");
+    if (staged_max > 0) HIP_TRY(h->stage.ensure((size_t)staged_max * rb));
+    h->rm_stats[0] = P.first;
+    h->rm_stats[1] = h->rm_stats[2] = 0;
+    h->rm_stats[3] = (int64_t)plan.size();
+    for (const RemoveChunk& c : plan) h->rm_stats[c.direct ? 1 : 2] += c.kept;
+    for (const RemoveChunk& c : plan) {
+        if (c.direct) {
+            HIP_TRY(launch_move_rows(h->codes, h->norms, sel->mask, prefix, nt, (int)rb, c.s0, c.s1, h->codes, h->norms, 0, s));
+        } else {
+            HIP_TRY(launch_move_rows(h->codes, h->norms, sel->mask, prefix, nt, (int)rb, c.s0, c.s1, (char*)h->stage.p,
+                                     nstage, c.d0, s));
+            HIP_TRY(hipMemcpyAsync(h->codes + (size_t)c.d0 * rb, h->stage.p, (size_t)c.kept * rb, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(h->norms + c.d0, nstage, (size_t)c.kept * 4, hipMemcpyDeviceToDevice, s));
+        }
+    }
+    const int64_t newn = P.kept;
+    // the freed tail: zero rows, +inf norms (grow / fx_index_reset)
+    HIP_TRY(hipMemsetAsync(h->codes + (size_t)newn * rb, 0, (size_t)(nt - newn) * rb, s));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(h->norms + newn), 0x7f800000u, (size_t)(nt - newn), s));
+    // max |y|^2 over the kept rows (a removed outlier's would keep the certification bound E wide for good)
+    HIP_TRY(hipMemsetAsync(h->max_sq_bits, 0, 4, s));
+    HIP_TRY(launch_norm_max(h->norms, newn, h->max_sq_bits, s));
+    // scan image: rows below the first removed one stay valid for the unchanged centre; update_scan_image
+    // rebuilds the rest at the next search.  Its freed tail: +inf row constants, zero F32S rows.
+    h->img_rows = std::min(h->img_rows, P.first);
+    if (h->cnorms.p) {
+        const int64_t hi = std::min<int64_t>(nt, (int64_t)(h->cnorms.bytes / 4));
+        if (newn < hi)
+            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)((float*)h->cnorms.p + newn), 0x7f800000u, (size_t)(hi - newn), s));
+        if (h->img_kind != IMG_NONE) {  // ... and its maximum over the rows that stay
+            HIP_TRY(hipMemsetAsync(h->max_sq_bits + 1, 0, 4, s));
+            HIP_TRY(launch_norm_max((const float*)h->cnorms.p, std::min<int64_t>(h->img_rows, hi), h->max_sq_bits + 1, s));
+        }
+    }
+    if (h->split.p) {
+        const int64_t hi = std::min<int64_t>(nt, (int64_t)(h->split.bytes / rb));
+        if (newn < hi) HIP_TRY(hipMemsetAsync((char*)h->split.p + (size_t)newn * rb, 0, (size_t)(hi - newn) * rb, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    h->ntotal = newn;
+    if (newn == 0) h->mu_rows = 0;  // as fx_index_reset leaves it
+    ++h->epoch;
+    h->rg_nq = -1;  // the last range search's result named the old rows
+    h->rg_total = 0;
+    graph_release(h);  // (its key would not notice a removal followed by an add of as many rows)
+    return FX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1400,7 +1567,8 @@ void fx_index_free(FxIndex* h) {
                           &h->cand2_i, &h->rq_f32, &h->rq_op, &h->rq_eps, &h->rq_rho, &h->rq_shift, &h->rq_gtau,
                           &h->rq_cand_d, &h->rq_cand_i, &h->rq_flag, &h->hk_ws, &h->hout, &h->conv, &h->rg_qin,
                           &h->rg_qf32, &h->rg_qop, &h->rg_eps, &h->rg_rho, &h->rg_shift, &h->rg_thr, &h->rg_cnt,
-                          &h->rg_cand, &h->rg_dist, &h->rg_sorted, &h->rg_temp, &h->rg_lims, &h->rg_D, &h->rg_I})
+                          &h->rg_cand, &h->rg_dist, &h->rg_sorted, &h->rg_temp, &h->rg_lims, &h->rg_D, &h->rg_I,
+                          &h->rm_ws})
             b->release();
         graph_release(h);
         if (h->ghq) (void)hipHostFree(h->ghq);
@@ -1442,6 +1610,13 @@ int fx_index_set_stream(FxIndex* h, void* stream) {
 int fx_index_set_option(FxIndex* h, const char* name, int64_t value) {
     if (!h || !name) return set_err(FX_E_ARG, "null argument");
     std::lock_guard<std::mutex> lk(h->mu);
+    if (strcmp(name, "remove_stage") == 0) {  // (bytes: the one option wider than an int)
+        if (value != 0 && (value < h->row_bytes || value > REMOVE_STAGE_MAX))
+            return set_err(FX_E_ARG, "option 'remove_stage': value out of range (%lld; 0 or %d .. %lld bytes)",
+                           (long long)value, h->row_bytes, (long long)REMOVE_STAGE_MAX);
+        h->opt.remove_stage = value;
+        return FX_OK;
+    }
     const char* why = nullptr;
     int* slot = h->opt.find(name, value, &why);
     if (!slot) return set_err(FX_E_ARG, "unknown option '%s'", name);
@@ -1671,6 +1846,42 @@ int fx_index_search_sel(FxIndex* h, const FxSelector* sel, int64_t nq, const voi
     // nothing selected (or an empty index): every slot missing, no scan
     if (h->ntotal == 0 || sel->rows == 0) return fill_missing(h, nq, k, D, I, out_mem);
     return do_search(h, nq, q, q_dtype, q_mem, k, D, I, out_mem, sel);
+}
+
+// ---- remove_ids (fx_remove.hip) --------------------------------------------
+
+int fx_index_remove_ids(FxIndex* h, const FxSelector* sel, int64_t* n_removed) {
+    if (!h) return set_err(FX_E_ARG, "null index");
+    if (!sel) return set_err(FX_E_ARG, "null selector");
+    if (!n_removed) return set_err(FX_E_ARG, "null n_removed");
+    *n_removed = 0;
+    if (sel->index != h) return set_err(FX_E_ARG, "remove_ids: the selector was created on another index");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (sel->ntotal != h->ntotal || sel->epoch != h->epoch)
+        return set_err(FX_E_ARG, "remove_ids: stale selector: it is a snapshot of %lld rows, the index now has %lld "
+                       "(rows were added or removed, or the index was reset since it was created)",
+                       (long long)sel->ntotal, (long long)h->ntotal);
+    DeviceGuard g(h->device);
+    if (!g.ok) return set_err(FX_E_HIP, "hipSetDevice(%d) failed", h->device);
+    {
+        const int rc = selector_counts(sel);
+        if (rc != FX_OK) return rc;
+    }
+    if (h->ntotal == 0 || sel->rows == 0) return FX_OK;  // nothing selected: nothing changes, the selector stays valid
+    const int rc = remove_rows(h, sel);
+    if (rc != FX_OK) return rc;
+    *n_removed = sel->rows;
+    return FX_OK;
+}
+
+int fx_index_last_remove_stats(FxIndex* h, int64_t* first, int64_t* direct_rows, int64_t* staged_rows, int64_t* chunks) {
+    if (!h || !first || !direct_rows || !staged_rows || !chunks) return set_err(FX_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    *first = h->rm_stats[0];
+    *direct_rows = h->rm_stats[1];
+    *staged_rows = h->rm_stats[2];
+    *chunks = h->rm_stats[3];
+    return FX_OK;
 }
 
 // the counts of the last search (after a device-resident one: synchronises the

@@ -1,5 +1,5 @@
 // fx_internal.h -- shared between the HIP translation units (fx_kernels.hip,
-// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip) and the host C ABI
+// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip) and the host C ABI
 // (fx_index.cpp): tiling constants, kernel parameter blocks, the launchers'
 // prototypes and their host-side helpers.  Not part of the public ABI
 // (include/fx_index.h).
@@ -348,6 +348,29 @@ hipError_t launch_sel_tiles(const uint32_t* mask, int64_t ntotal, int* tiles, Se
 // [qtile][split][TILE_Q][KP] candidate lists, every split's written
 hipError_t launch_scan_sel(int st_dt, int metric, const ScanParams& p, const uint32_t* mask, const int* tiles,
                            const SelCounts* cnt, hipStream_t s);
+// remove_ids (fx_remove.hip): the in-place compaction of codes / norms under a
+// selector's row mask (a set bit: the row is REMOVED).
+// launch_keep_prefix: prefix[w] = kept rows before mask word w (sel_mask_words
+// words), gp[g] = the same at row 1024 g (rm_groups entries), bsum:
+// rm_prefix_blocks words of scratch, info[0] = the first removed row
+// (0xffffffff: none), info[1] = the kept total.
+constexpr int RM_WORDS_PER_BLOCK = 256;  // mask words per workgroup of the prefix kernels
+constexpr int64_t RM_GROUP_ROWS = 1024;  // rows per gp entry (32 mask words)
+inline int64_t rm_prefix_blocks(int64_t ntotal) {
+    return (sel_mask_words(ntotal) + RM_WORDS_PER_BLOCK - 1) / RM_WORDS_PER_BLOCK;
+}
+inline int64_t rm_groups(int64_t ntotal) { return (sel_mask_words(ntotal) + 31) / 32; }
+hipError_t launch_keep_prefix(const uint32_t* mask, int64_t ntotal, unsigned* prefix, unsigned* gp, unsigned* bsum,
+                              unsigned* info, hipStream_t s);
+// kept rows r of the source rows [s0, s1) (and their norms) -> row prefix(r) -
+// dbase of dst_codes / dst_norms.  The caller orders the launches (DESIGN.md
+// "row removal"): dst is the index's own arrays only when every destination
+// row lies below s0, else a staging buffer.
+hipError_t launch_move_rows(const char* codes, const float* norms, const uint32_t* mask, const unsigned* prefix,
+                            int64_t ntotal, int row_bytes, int64_t s0, int64_t s1, char* dst_codes, float* dst_norms,
+                            int64_t dbase, hipStream_t s);
+// bits[0] <- max(bits[0], float bits of the largest of norms[0, n)) (atomicMax)
+hipError_t launch_norm_max(const float* norms, int64_t n, unsigned* bits, hipStream_t s);
 // fp32 code rows [r0, r1) -> their F32S scan image (same row stride)
 // (centred by mu when non-null), with the image rows' |v|^2 -> cnorms and their
 // maximum -> cmax_bits (atomicMax)

@@ -8,7 +8,9 @@ as faiss``:
 * ``IndexFlatL2(d)`` / ``IndexFlatIP(d)`` with ``.d``, ``.ntotal``,
   ``.metric_type``, ``.is_trained``, ``.add(x)``, ``.search(x, k) -> (D, I)``,
   ``.range_search(x, radius) -> (lims, D, I)``, ``.reset()``,
-  ``.reconstruct_n(i0, n)``;
+  ``.reconstruct_n(i0, n)``, ``.remove_ids(sel_or_ids) -> n_removed`` (the
+  kept rows keep their order and are renumbered densely, compacted in place
+  on the GPU);
 * filtered search, ``index.search(x, k, params=SearchParameters(sel=...))``
   with ``IDSelectorRange``, ``IDSelectorArray``, ``IDSelectorBatch``,
   ``IDSelectorBitmap`` and ``IDSelectorNot``: only the selected ids are ranked
@@ -72,7 +74,7 @@ class IDSelector:
     returns (row + the index's id offset).  The device image a search needs
     (``FxSelector``: row mask + live tiles) is built on first use and cached
     per index for the index's current ``ntotal`` and id offset; after ``add``
-    / ``reset`` it is rebuilt transparently."""
+    / ``reset`` / ``remove_ids`` it is rebuilt transparently."""
 
     _kind = -1
 
@@ -243,7 +245,8 @@ class _FlatIndex:
     """Common implementation of IndexFlatL2 / IndexFlatIP."""
 
     _id_offset = 0
-    _resets = 0  # reset() calls: with ntotal and the id offset, what a built selector is a snapshot of
+    _resets = 0  # reset() and remove_ids() calls: with ntotal and the id offset, what a built selector is a
+                 # snapshot of (a removal followed by an add of as many rows restores ntotal, not the rows)
 
     metric_type: int = METRIC_L2
     _lib = lib  # the ctypes build this index lives in (the diagnostic build: diag.py)
@@ -447,6 +450,28 @@ class _FlatIndex:
     def reset(self) -> None:
         self._check(self._lib.fx_index_reset(self._h))
         self._resets += 1
+
+    def remove_ids(self, x) -> int:
+        """``IndexFlatCodes.remove_ids``: remove the rows ``x`` selects -- an
+        ``IDSelector`` of this module, or ids as ``IDSelectorBatch`` takes them
+        (array-like, or an int64 tensor on the index's GPU).  The kept rows
+        keep their order and are renumbered densely (row r again has id r +
+        the id offset).  Returns the number of rows removed."""
+        sel = x if isinstance(x, IDSelector) else IDSelectorBatch(x)
+        self._bind_stream(_is_device_tensor(sel._spec()[1]))
+        n = ctypes.c_int64(0)
+        self._check(self._lib.fx_index_remove_ids(self._h, sel._handle(self), ctypes.byref(n)))
+        if n.value:
+            self._resets += 1  # every built selector, this one included, is a snapshot of the old rows
+        return n.value
+
+    def last_remove_stats(self) -> dict:
+        """The plan of the last ``remove_ids`` that removed a row: ``first``
+        removed row, kept rows above it moved in place (``direct_rows``) and
+        through the staging buffer (``staged_rows``), ``chunks`` launched."""
+        v = [ctypes.c_int64(0) for _ in range(4)]
+        self._check(self._lib.fx_index_last_remove_stats(self._h, *(ctypes.byref(x) for x in v)))
+        return dict(zip(("first", "direct_rows", "staged_rows", "chunks"), (x.value for x in v)))
 
     def reserve(self, n: int) -> None:
         self._check(self._lib.fx_index_reserve(self._h, int(n)))

@@ -9,6 +9,8 @@ Extensions (keyword-only, defaults reproduce the reference): ``dtype`` of the
 HBM codes ("float32" like the reference, or "bfloat16"/"float16") and the
 GPU ``device``.  ``add_vectors``/``search`` also accept torch tensors that
 already live on the GPU (encoder hand-off without ``.cpu().numpy()``).
+``remove_vectors(ids)`` deletes documents' rows in place (the reference can
+only rebuild the whole index).
 """
 from __future__ import annotations
 
@@ -123,6 +125,29 @@ class FAISSVectorStore:
         except Exception as e:  # noqa: BLE001 -- same contract as search
             logger.error("search_radius failed: %s", e)
             return np.array([]), []
+
+    def remove_vectors(self, ids) -> int:
+        """Remove every row whose document id is in ``ids`` (extension; the
+        index's ``remove_ids``: compacted in place on the GPU, the kept rows
+        keep their order).  An id that occurs several times removes all its
+        rows; unknown ids are ignored; rows past the end of ``doc_ids`` (see
+        ``add_vectors``) are left alone.  The same positions go from
+        ``doc_ids``, so rows and ids stay aligned.  Returns the number of rows
+        removed.  Errors are logged and raised again, as in ``load_index``."""
+        try:
+            gone = set(int(a) for a in ids)
+            n_rows = min(len(self.doc_ids), self.index.ntotal)
+            rows = [r for r in range(n_rows) if self.doc_ids[r] in gone]
+            if not rows:
+                return 0
+            n = int(self.index.remove_ids(np.asarray(rows, dtype=np.int64)))
+            dropped = set(rows)
+            self.doc_ids = [doc for r, doc in enumerate(self.doc_ids) if r not in dropped]
+            logger.info("remove: %d rows -> ntotal %d", n, self.index.ntotal)
+            return n
+        except Exception as e:
+            logger.error("remove failed: %s", e)
+            raise
 
     def save_index(self, filepath: Optional[str] = None):
         """faiss_store.py:83-97: IxF2 index file + pickle-protocol-4 id list

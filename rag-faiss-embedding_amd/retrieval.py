@@ -245,6 +245,22 @@ class RetrievalEngine:
         return documents_within(self.index, self.doc_ids, self.store, self.embed(texts),
                                 max_distance=max_distance, min_score=min_score)
 
+    def remove_documents(self, ids: Iterable[int]) -> int:
+        """Remove every index row whose document id is in ``ids`` (all rows of
+        an id held by several; unknown ids are ignored; rows past the end of
+        ``doc_ids`` are left alone) and the same positions of the engine's own
+        ``doc_ids`` list.  Returns the number of rows removed.  Errors
+        propagate."""
+        gone = np.fromiter((int(a) for a in ids), dtype=np.int64)
+        n_rows = min(len(self.doc_ids), int(self.index.ntotal))
+        rows = np.flatnonzero(np.isin(np.asarray(self.doc_ids[:n_rows], dtype=np.int64), gone)).astype(np.int64)
+        if rows.size == 0:
+            return 0
+        n = int(self.index.remove_ids(rows))
+        dropped = set(rows.tolist())
+        self.doc_ids = [doc for r, doc in enumerate(self.doc_ids) if r not in dropped]
+        return n
+
     def search_one(self, text: str, k: int = 5) -> List[Dict]:
         """The reference's single-query call shape (rag_datastore_manager.py:211)."""
         out = self.search([text], k)

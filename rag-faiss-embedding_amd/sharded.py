@@ -38,6 +38,10 @@ class ShardedIndexFlatL2:
     results need a different exchange than the fixed (nq x k) all_gather.
     A caller that wants it runs ``local.range_search`` per rank (ids are
     global through the id offset) and concatenates.
+
+    ``remove_ids`` is not offered either (as there is no ``reset``): a removal
+    renumbers a shard's rows densely, so the ranks would have to agree on new
+    shard offsets and ``n_total`` before the next search.
     """
 
     def __init__(self, d: int, n_total: int, dtype: str = "float32", group=None, device: Optional[int] = None,
