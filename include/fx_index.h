@@ -22,6 +22,13 @@
  *   index.remove_ids(sel) (documents re-crawled,     faiss_Index_remove_ids       fx_index_remove_ids
  *                          edited or deleted; see                                  + fx_selector_create
  *                          "row removal" below)
+ *   IndexIDMap2(index)    (ids that survive a        faiss_IndexIDMap2_new        (a mode of the index; see
+ *     .add_with_ids        removal: one document id  faiss_Index_add_with_ids      "stable ids" below)
+ *     (x, ids)             on its chunk rows)                                     fx_index_add_with_ids
+ *     .id_map                                        faiss_IndexIDMap_id_map      fx_index_get_ids
+ *     .reconstruct(id)                               faiss_Index_reconstruct      fx_index_rows_of_ids
+ *                                                                                  + fx_index_reconstruct_n
+ *   (is it an IDMap?)     --                         faiss_IndexIDMap_cast        fx_index_has_ids
  *   index.ntotal          faiss_store.py:53          faiss_Index_ntotal           fx_index_ntotal
  *   (re)IndexFlatL2(d)    faiss_store.py:126         faiss_Index_reset            fx_index_reset
  *   faiss.write_index     faiss_store.py:91,         faiss_write_index_fname      fx_index_write
@@ -132,7 +139,8 @@ int fx_index_set_stream(FxIndex* index, void* stream);
  * build libfx_index_diag.so adds test hooks -- "force_fallback",
  * "scan_dbg" -- that the product library does not have.) */
 int fx_index_set_option(FxIndex* index, const char* name, int64_t value);
-/* Global id of local row 0 (row-sharded multi-GPU: shard offset). */
+/* Global id of local row 0 (row-sharded multi-GPU: shard offset).  A non-zero
+ * offset on a labelled index ("stable ids" below): FX_E_ARG. */
 int fx_index_set_id_offset(FxIndex* index, int64_t offset);
 
 int fx_index_dim(const FxIndex* index, int* out);
@@ -269,6 +277,73 @@ int fx_index_remove_ids(FxIndex* index, const FxSelector* sel, int64_t* n_remove
 int fx_index_last_remove_stats(FxIndex* index, int64_t* first, int64_t* direct_rows, int64_t* staged_rows,
                                int64_t* chunks);
 
+/* ---- stable ids: faiss IndexIDMap / IndexIDMap2 ---------------------------
+ *
+ *   faiss (Python)                                  faiss C API                        this ABI
+ *   IndexIDMap(index) / IndexIDMap2(index)          faiss_IndexIDMap_new /             (the mode below)
+ *                                                   faiss_IndexIDMap2_new
+ *   index.add_with_ids(x, ids)                      faiss_Index_add_with_ids           fx_index_add_with_ids
+ *   index.id_map                                    faiss_IndexIDMap_id_map            fx_index_get_ids
+ *   IndexIDMap2.rev_map / reconstruct(id)           faiss_Index_reconstruct            fx_index_rows_of_ids
+ *   (downcast test)                                 faiss_IndexIDMap_cast              fx_index_has_ids
+ *
+ * An index may carry a LABEL ARRAY: one caller-chosen int64 per row, resident
+ * on the device, grown with the rows and compacted with them by
+ * fx_index_remove_ids, so the ids a caller holds survive removals.  It is a
+ * mode of the index, decided by the first add into an EMPTY index:
+ * fx_index_add_with_ids turns it on, fx_index_add leaves (or turns) it off;
+ * on a non-empty index the add of the other mode is FX_E_ARG (faiss: "add does
+ * not make sense with IndexIDMap" / "add_with_ids not implemented for this
+ * type of index").  fx_index_reset empties the index and clears the mode.
+ * Labels and id_offset exclude each other: fx_index_add_with_ids with a
+ * non-zero offset set, and fx_index_set_id_offset(non-zero) on a labelled
+ * index, are FX_E_ARG.
+ *
+ * Labels are arbitrary int64: negative values, values above 2^32 and
+ * duplicates are legal (one document id on several chunk rows).  -1 is legal
+ * too but cannot be told from the "missing slot" marker in results.
+ *
+ * On a labelled index
+ *   - fx_index_search, fx_index_search_sel and fx_index_range_search /
+ *     fx_index_range_result return labels in I (empty slots stay -1).  Ranking
+ *     stays by (distance, ROW), as faiss's IndexIDMap (the inner index ranks,
+ *     then ids are translated): ties break on insertion order, not on label,
+ *     and a range result stays ordered by ascending row within a query;
+ *   - fx_selector_create takes the same three kinds, whose ids, range bounds
+ *     and bitmap bit positions now mean LABELS: a row is selected iff its label
+ *     is a member.  Bitmap membership is faiss's: (uint64_t)label >> 3 < n and
+ *     the bit set, so negative labels are never members.  `invert`, the
+ *     snapshot and the staleness rules are unchanged;
+ *   - fx_index_remove_ids keeps its contract; the labels move with their rows;
+ *   - fx_index_write writes faiss's IndexIDMap2 file: fourcc "IxM2", then the
+ *     header fields of IxF2 (i32 d, i64 ntotal, i64 1<<20, i64 1<<20, u8
+ *     is_trained, i32 metric), then the complete IxF2 file as the sub-index,
+ *     then i64 n and n int64 labels.  (This restates faiss's write_index for
+ *     IndexIDMap2 as remembered; it is not checked against a faiss build.)
+ *     fx_index_read accepts "IxF2", "IxMp" (IndexIDMap) and "IxM2"; a file cut
+ *     short anywhere is FX_E_IO and no index is returned. */
+
+/* index.add_with_ids(x, ids) (IndexIDMap::add_with_ids): fx_index_add of the
+ * n rows of x, row i labelled ids[i].  ids: n int64 on ids_mem.  With
+ * FX_MEM_DEVICE rows and ids it is stream-ordered like fx_index_add.  n == 0:
+ * FX_OK and nothing changes (the mode included).  FX_E_ARG: null x or ids with
+ * n > 0, an unlabelled index that has rows, a non-zero id_offset. */
+int fx_index_add_with_ids(FxIndex* index, int64_t n, const void* x, int x_dtype, int x_mem, const int64_t* ids,
+                          int ids_mem);
+/* *out = 1 when the index is in the labelled mode, else 0. */
+int fx_index_has_ids(const FxIndex* index, int* out);
+/* IndexIDMap::id_map: the labels of rows [i0, i0 + n) -> out (host or
+ * device; a host copy blocks).  FX_E_ARG: an index without labels, a range
+ * outside [0, ntotal]. */
+int fx_index_get_ids(FxIndex* index, int64_t i0, int64_t n, int64_t* out, int out_mem);
+/* IndexIDMap2::rev_map: rows[i] = the LAST row (the one added last) whose
+ * label is ids[i], -1 when no row carries it; repeated entries of ids each
+ * get the answer.  ids and rows: n int64 each, host or device (device buffers
+ * are read / written stream-ordered; a host `rows` blocks).  One pass over the
+ * label array whatever n.  FX_E_ARG on an index without labels;
+ * FX_E_UNSUPPORTED for n > 2^31-1. */
+int fx_index_rows_of_ids(FxIndex* index, const int64_t* ids, int64_t n, int ids_mem, int64_t* rows, int rows_mem);
+
 /* Number of queries of the last search whose top-k could not be certified
  * from the scan's candidate margin and were re-scanned with a wide candidate
  * set (after an FX_MEM_DEVICE search this synchronises the index stream). */
@@ -300,7 +375,9 @@ int fx_index_reconstruct_n(FxIndex* index, int64_t i0, int64_t n, float* out);
 
 /* faiss.write_index / faiss.read_index on the IxF2 format (faiss_store.py:
  * 91,106): fourcc "IxF2", i32 d, i64 ntotal, i64 1<<20, i64 1<<20,
- * u8 is_trained, i32 metric, i64 ntotal*d, f32 codes. */
+ * u8 is_trained, i32 metric, i64 ntotal*d, f32 codes.  A labelled index is
+ * written as "IxM2" around that file, and read back labelled ("stable ids"
+ * above). */
 int fx_index_write(FxIndex* index, const char* path);
 int fx_index_read(const char* path, int storage_dtype, int device, FxIndex** out);
 

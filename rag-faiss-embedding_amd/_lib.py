@@ -64,6 +64,10 @@ SIGNATURES = {
     "fx_index_remove_ids": (_i, [_vp, _vp, ctypes.POINTER(_i64)]),
     "fx_index_last_remove_stats": (_i, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                         ctypes.POINTER(_i64)]),
+    "fx_index_add_with_ids": (_i, [_vp, _i64, _vp, _i, _i, _vp, _i]),
+    "fx_index_has_ids": (_i, [_vp, ctypes.POINTER(_i)]),
+    "fx_index_get_ids": (_i, [_vp, _i64, _i64, _vp, _i]),
+    "fx_index_rows_of_ids": (_i, [_vp, _vp, _i64, _i, _vp, _i]),
     "fx_index_last_fallbacks": (_i, [_vp, ctypes.POINTER(_i64)]),
     "fx_index_last_scan_plan": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "fx_index_last_exact_fallbacks": (_i, [_vp, ctypes.POINTER(_i64)]),

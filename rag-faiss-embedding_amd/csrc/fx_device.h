@@ -279,6 +279,12 @@ __device__ __forceinline__ float ord2f(unsigned o) {
     return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
 
+// the id a result slot reports for local row `row` (0 <= row < ntotal): its
+// label on a labelled index (fx_idmap.hip), else row + id_offset
+__device__ __forceinline__ int64_t result_id(const int64_t* __restrict__ labels, int64_t row, int64_t id_offset) {
+    return labels ? labels[row] : row + id_offset;
+}
+
 // ---------------------------------------------------------------------------
 // block-wide (256 threads) top-K in LDS for any K <= FX_BIG_K: the paths that
 // are not the fused scan's fixed KP = 32 lists (k > KP refine, the exact

@@ -98,7 +98,8 @@ __global__ void k_hk_offsets(int* __restrict__ offs, int nseg, int seglen) {
 // first k keys of each sorted segment -> D / I (rows q0 .. q0 + nseg of the output)
 __global__ __launch_bounds__(HK_THREADS) void k_hk_out(const uint64_t* __restrict__ sorted, int64_t seglen, int nseg,
                                                        int k, int idbits, int metric, int64_t id_offset,
-                                                       float* __restrict__ D, int64_t* __restrict__ I) {
+                                                       const int64_t* __restrict__ labels, float* __restrict__ D,
+                                                       int64_t* __restrict__ I) {
     const int64_t total = (int64_t)nseg * k;
     const uint64_t idmask = (idbits >= 64) ? ~0ull : ((1ull << idbits) - 1);
     for (int64_t i = (int64_t)blockIdx.x * HK_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * HK_THREADS) {
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(HK_THREADS) void k_hk_out(const uint64_t* __restric
             const uint64_t key = sorted[q * seglen + t];
             const float f = ord2f((unsigned)(key >> idbits));
             D[i] = metric == L2 ? f : -f;
-            I[i] = (int64_t)(key & idmask) + id_offset;
+            I[i] = result_id(labels, (int64_t)(key & idmask), id_offset);
         } else {
             D[i] = metric == L2 ? FLT_MAX : -FLT_MAX;
             I[i] = -1;
@@ -221,7 +222,7 @@ hipError_t launch_hugek_search(const HugeKParams& p, void* ws, size_t ws_bytes, 
             if (e != hipSuccess) return e;
         }
         hipLaunchKernelGGL(k_hk_out, dim3(grid_for((int64_t)nb * p.k)), dim3(HK_THREADS), 0, s, sorted, p.ntotal, nb,
-                           p.k, idbits, p.metric, p.id_offset, p.D + b0 * p.k, p.I + b0 * p.k);
+                           p.k, idbits, p.metric, p.id_offset, p.labels, p.D + b0 * p.k, p.I + b0 * p.k);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;

@@ -283,6 +283,14 @@ struct FxIndex {
     int64_t ntotal = 0, cap_rows = 0, id_offset = 0;
     char* codes = nullptr;
     float* norms = nullptr;
+    // stable ids (fx_idmap.hip): in the labelled mode (has_ids) row r's label is
+    // labels[r]; the buffer holds label_cap >= cap_rows entries (grow_labels).
+    // labels_alt: the second buffer a removal compacts into, then swapped in.
+    bool has_ids = false;
+    int64_t* labels = nullptr;
+    int64_t* labels_alt = nullptr;
+    int64_t label_cap = 0, label_alt_cap = 0;
+    DevBuf idm_ws;  // sort workspace of a selector's id list / rows_of_ids, staged host ids
     // device words: [0] max |y|^2 of the stored rows, [1] max srcC of the scan
     // image (F32S / C16), as float bits (non-negative floats order as uints)
     unsigned* max_sq_bits = nullptr;
@@ -387,8 +395,30 @@ namespace {
 
 int check_dtype(int dt) { return dt == FX_F32 || dt == FX_BF16 || dt == FX_F16; }
 
+// the labelled mode's buffer follows the rows' capacity (a no-op without
+// labels, or when it is large enough): the ntotal labels are carried over
+hipError_t grow_labels(FxIndex* h) {
+    if (!h->has_ids || (h->labels && h->label_cap >= h->cap_rows)) return hipSuccess;
+    const int64_t cap = std::max<int64_t>(h->cap_rows, TILE_R);
+    int64_t* labels = nullptr;
+    hipError_t e = hipMalloc((void**)&labels, (size_t)cap * 8);
+    if (e != hipSuccess) return e;
+    hipStream_t s = h->stream();
+    if (h->labels && h->ntotal > 0)
+        e = hipMemcpyAsync(labels, h->labels, (size_t)h->ntotal * 8, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // (searches in flight still read the old buffer)
+    if (e != hipSuccess) {
+        (void)hipFree(labels);
+        return e;
+    }
+    if (h->labels) (void)hipFree(h->labels);
+    h->labels = labels;
+    h->label_cap = cap;
+    return hipSuccess;
+}
+
 hipError_t grow(FxIndex* h, int64_t need_rows) {
-    if (need_rows <= h->cap_rows) return hipSuccess;
+    if (need_rows <= h->cap_rows) return grow_labels(h);
     int64_t cap = round_up(std::max<int64_t>(need_rows, h->cap_rows + h->cap_rows / 2), TILE_R);
     char* codes = nullptr;
     float* norms = nullptr;
@@ -420,7 +450,7 @@ hipError_t grow(FxIndex* h, int64_t need_rows) {
     h->codes = codes;
     h->norms = norms;
     h->cap_rows = cap;
-    return hipSuccess;
+    return grow_labels(h);
 }
 
 // split count whose live workgroups (one per CU: the scan's LDS) fill whole
@@ -846,6 +876,7 @@ hipError_t plan_search(FxIndex* h, int64_t nq, const void* qdev, int q_dtype, in
     rp.qrho = pp.qrho;
     rp.qshift = pp.qshift;
     rp.id_offset = h->id_offset;
+    rp.labels = h->has_ids ? h->labels : nullptr;
     rp.D = Dd;
     rp.I = Id;
     rp.n_flag = words ? words + 1 : (int*)h->flag.p;
@@ -946,7 +977,7 @@ hipError_t enqueue_fallback(FxIndex* h, SearchPlan& P, hipStream_t s) {
     }
     return launch_exact_fallback(h->dtype, h->metric, h->codes, h->row_bytes, h->kdim, h->ntotal, P.rp.qf32,
                                  P.n_exact, P.k, h->id_offset, (float*)h->fbc_d.p, (int*)h->fbc_i.p, P.rp.D, P.rp.I,
-                                 s, P.sel ? P.sel->mask : nullptr);
+                                 s, P.sel ? P.sel->mask : nullptr, P.rp.labels);
 }
 
 // Host-output searches (the reference's call form) return through ONE packed
@@ -1182,6 +1213,7 @@ int do_search_hugek(FxIndex* h, int64_t nq, const void* q, int q_dtype, int q_me
     p.nq = nq;
     p.k = k;
     p.id_offset = h->id_offset;
+    p.labels = h->has_ids ? h->labels : nullptr;
     p.D = Dd;
     p.I = Id;
     HIP_TRY(launch_hugek_search(p, h->hk_ws.p, h->hk_ws.bytes, qb, s));
@@ -1225,7 +1257,9 @@ std::vector<uint64_t> graph_key(const FxIndex* h, int64_t nq, int q_dtype, int k
             (uint64_t)(uintptr_t)h->rq_f32.p, (uint64_t)(uintptr_t)h->rq_op.p, (uint64_t)(uintptr_t)h->rq_eps.p,
             (uint64_t)(uintptr_t)h->rq_rho.p, (uint64_t)(uintptr_t)h->rq_shift.p, (uint64_t)(uintptr_t)h->rq_gtau.p,
             (uint64_t)(uintptr_t)h->rq_cand_d.p, (uint64_t)(uintptr_t)h->rq_cand_i.p,
-            (uint64_t)(uintptr_t)h->rq_flag.p};
+            (uint64_t)(uintptr_t)h->rq_flag.p,
+            // the label buffer the refine reads (null without labels): growth and a removal's swap replace it
+            (uint64_t)(uintptr_t)(h->has_ids ? h->labels : nullptr)};
 }
 
 void graph_release(FxIndex* h) {
@@ -1464,6 +1498,20 @@ int remove_rows(FxIndex* h, const FxSelector* sel) {
         }
     }
     const int64_t newn = P.kept;
+    if (h->has_ids) {
+        // the labels follow their rows: compacted out of place into the second buffer, which takes over
+        // (searches enqueued before this call are done with the old one: the sync below precedes any reuse)
+        if (!h->labels_alt || h->label_alt_cap < h->label_cap) {
+            if (h->labels_alt) (void)hipFree(h->labels_alt);
+            h->labels_alt = nullptr;
+            h->label_alt_cap = 0;
+            HIP_TRY(hipMalloc((void**)&h->labels_alt, (size_t)h->label_cap * 8));
+            h->label_alt_cap = h->label_cap;
+        }
+        HIP_TRY(launch_compact_labels(h->labels, sel->mask, prefix, nt, h->labels_alt, s));
+        std::swap(h->labels, h->labels_alt);
+        std::swap(h->label_cap, h->label_alt_cap);
+    }
     // the freed tail: zero rows, +inf norms (grow / fx_index_reset)
     HIP_TRY(hipMemsetAsync(h->codes + (size_t)newn * rb, 0, (size_t)(nt - newn) * rb, s));
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(h->norms + newn), 0x7f800000u, (size_t)(nt - newn), s));
@@ -1559,6 +1607,9 @@ void fx_index_free(FxIndex* h) {
         if (h->user_stream) (void)hipStreamSynchronize(h->user_stream);
         if (h->codes) (void)hipFree(h->codes);
         if (h->norms) (void)hipFree(h->norms);
+        if (h->labels) (void)hipFree(h->labels);
+        if (h->labels_alt) (void)hipFree(h->labels_alt);
+        h->idm_ws.release();
         if (h->max_sq_bits) (void)hipFree(h->max_sq_bits);
         if (h->dev_drop) (void)hipFree(h->dev_drop);
         for (DevBuf* b : {&h->qin, &h->qf32, &h->qop, &h->qeps, &h->cand_d, &h->cand_i, &h->dws, &h->iws, &h->flag,
@@ -1634,6 +1685,8 @@ int fx_index_set_option(FxIndex* h, const char* name, int64_t value) {
 int fx_index_set_id_offset(FxIndex* h, int64_t off) {
     if (!h || off < 0) return set_err(FX_E_ARG, "bad index/offset");
     std::lock_guard<std::mutex> lk(h->mu);
+    if (off != 0 && h->has_ids)
+        return set_err(FX_E_ARG, "set_id_offset: the index carries labels (add_with_ids); ids are the labels, not row + offset");
     h->id_offset = off;
     return FX_OK;
 }
@@ -1667,15 +1720,9 @@ int fx_index_reserve(FxIndex* h, int64_t n) {
     return FX_OK;
 }
 
-int fx_index_add(FxIndex* h, int64_t n, const void* x, int x_dtype, int x_mem) {
-    if (!h) return set_err(FX_E_ARG, "null index");
-    if (n < 0) return set_err(FX_E_ARG, "negative n");
-    if (n == 0) return FX_OK;
-    if (!x) return set_err(FX_E_ARG, "null x");
-    if (!check_dtype(x_dtype)) return set_err(FX_E_ARG, "bad x dtype %d", x_dtype);
-    if ((int64_t)h->ntotal + n >= (int64_t)INT32_MAX) return set_err(FX_E_UNSUPPORTED, "more than 2^31-1 rows per shard");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard g(h->device);
+// the append of fx_index_add / fx_index_add_with_ids (arguments validated, the
+// index locked): rows [ntotal, ntotal + n) <- x; ntotal is the caller's to advance
+static int append_rows(FxIndex* h, int64_t n, const void* x, int x_dtype, int x_mem) {
     hipStream_t s = h->stream();
     HIP_TRY(grow(h, h->ntotal + n));
     const size_t xes = dtype_size(x_dtype);
@@ -1696,7 +1743,120 @@ int fx_index_add(FxIndex* h, int64_t n, const void* x, int x_dtype, int x_mem) {
             HIP_TRY(hipStreamSynchronize(s));  // staging buffer reuse
         }
     }
+    return FX_OK;
+}
+
+static int check_add_args(const FxIndex* h, int64_t n, const void* x, int x_dtype) {
+    if (!x) return set_err(FX_E_ARG, "null x");
+    if (!check_dtype(x_dtype)) return set_err(FX_E_ARG, "bad x dtype %d", x_dtype);
+    if ((int64_t)h->ntotal + n >= (int64_t)INT32_MAX) return set_err(FX_E_UNSUPPORTED, "more than 2^31-1 rows per shard");
+    return FX_OK;
+}
+
+int fx_index_add(FxIndex* h, int64_t n, const void* x, int x_dtype, int x_mem) {
+    if (!h) return set_err(FX_E_ARG, "null index");
+    if (n < 0) return set_err(FX_E_ARG, "negative n");
+    if (n == 0) return FX_OK;
+    if (const int rc = check_add_args(h, n, x, x_dtype); rc != FX_OK) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->has_ids && h->ntotal > 0)
+        return set_err(FX_E_ARG, "add does not make sense on an index with labels: use add_with_ids");
+    h->has_ids = false;  // the first add into an empty index decides the mode
+    DeviceGuard g(h->device);
+    if (const int rc = append_rows(h, n, x, x_dtype, x_mem); rc != FX_OK) return rc;
     h->ntotal += n;
+    return FX_OK;
+}
+
+// ---- stable ids (fx_idmap.hip) ----------------------------------------------
+
+int fx_index_add_with_ids(FxIndex* h, int64_t n, const void* x, int x_dtype, int x_mem, const int64_t* ids,
+                          int ids_mem) {
+    if (!h) return set_err(FX_E_ARG, "null index");
+    if (n < 0) return set_err(FX_E_ARG, "negative n");
+    if (n == 0) return FX_OK;
+    if (!ids) return set_err(FX_E_ARG, "add_with_ids: null ids");
+    if (ids_mem != FX_MEM_HOST && ids_mem != FX_MEM_DEVICE) return set_err(FX_E_ARG, "bad ids_mem %d", ids_mem);
+    if (const int rc = check_add_args(h, n, x, x_dtype); rc != FX_OK) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->has_ids && h->ntotal > 0)
+        return set_err(FX_E_ARG, "add_with_ids not implemented for an index that holds rows without labels");
+    if (h->id_offset != 0)
+        return set_err(FX_E_ARG, "add_with_ids: the index has id offset %lld; labels and an id offset exclude each other",
+                       (long long)h->id_offset);
+    DeviceGuard g(h->device);
+    const bool was = h->has_ids;
+    h->has_ids = true;  // (grow carries / allocates the label buffer from here on)
+    int rc = append_rows(h, n, x, x_dtype, x_mem);
+    if (rc == FX_OK) {
+        hipStream_t s = h->stream();
+        hipError_t e = hipMemcpyAsync(h->labels + h->ntotal, ids, (size_t)n * 8,
+                                      ids_mem == FX_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s);
+        // (host ids: the caller's array may go when the call returns)
+        if (e == hipSuccess && ids_mem == FX_MEM_HOST) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) rc = set_err(FX_E_HIP, "add_with_ids: copying the labels: %s", hipGetErrorString(e));
+    }
+    if (rc != FX_OK) {
+        h->has_ids = was;
+        return rc;
+    }
+    h->ntotal += n;
+    return FX_OK;
+}
+
+int fx_index_has_ids(const FxIndex* h, int* out) {
+    if (!h || !out) return set_err(FX_E_ARG, "null argument");
+    *out = h->has_ids ? 1 : 0;
+    return FX_OK;
+}
+
+int fx_index_get_ids(FxIndex* h, int64_t i0, int64_t n, int64_t* out, int out_mem) {
+    if (!h) return set_err(FX_E_ARG, "null index");
+    if (i0 < 0 || n < 0) return set_err(FX_E_ARG, "get_ids: negative range");
+    if (out_mem != FX_MEM_HOST && out_mem != FX_MEM_DEVICE) return set_err(FX_E_ARG, "bad out_mem %d", out_mem);
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->has_ids) return set_err(FX_E_ARG, "get_ids: the index carries no labels (it was not filled by add_with_ids)");
+    if (i0 > h->ntotal || n > h->ntotal - i0)
+        return set_err(FX_E_ARG, "get_ids: rows [%lld, %lld) outside the index's %lld", (long long)i0,
+                       (long long)(i0 + n), (long long)h->ntotal);
+    if (n == 0) return FX_OK;
+    if (!out) return set_err(FX_E_ARG, "null buffer");
+    DeviceGuard g(h->device);
+    hipStream_t s = h->stream();
+    HIP_TRY(hipMemcpyAsync(out, h->labels + i0, (size_t)n * 8,
+                           out_mem == FX_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+    if (out_mem == FX_MEM_HOST) HIP_TRY(hipStreamSynchronize(s));
+    return FX_OK;
+}
+
+int fx_index_rows_of_ids(FxIndex* h, const int64_t* ids, int64_t n, int ids_mem, int64_t* rows, int rows_mem) {
+    if (!h) return set_err(FX_E_ARG, "null index");
+    if (n < 0) return set_err(FX_E_ARG, "negative n");
+    if ((ids_mem != FX_MEM_HOST && ids_mem != FX_MEM_DEVICE) || (rows_mem != FX_MEM_HOST && rows_mem != FX_MEM_DEVICE))
+        return set_err(FX_E_ARG, "bad ids_mem / rows_mem");
+    if (n > 0 && (!ids || !rows)) return set_err(FX_E_ARG, "null buffer");
+    if (n > (int64_t)INT32_MAX) return set_err(FX_E_UNSUPPORTED, "rows_of_ids: more than 2^31-1 ids per call");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->has_ids) return set_err(FX_E_ARG, "rows_of_ids: the index carries no labels (it was not filled by add_with_ids)");
+    if (n == 0) return FX_OK;
+    DeviceGuard g(h->device);
+    hipStream_t s = h->stream();
+    // workspace: [sort | staged host ids | device rows of a host output]
+    size_t sort_bytes = 0;
+    HIP_TRY(idmap_sort_bytes(n, true, &sort_bytes));
+    const size_t nb = (size_t)round_up(n * 8, 256);
+    HIP_TRY(h->idm_ws.ensure(sort_bytes + 2 * nb));
+    char* base = (char*)h->idm_ws.p;
+    const int64_t* dids = ids;
+    if (ids_mem == FX_MEM_HOST) {
+        HIP_TRY(hipMemcpyAsync(base + sort_bytes, ids, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        dids = (const int64_t*)(base + sort_bytes);
+    }
+    int64_t* drows = rows_mem == FX_MEM_HOST ? (int64_t*)(base + sort_bytes + nb) : rows;
+    HIP_TRY(launch_rows_of_labels(h->labels, h->ntotal, dids, n, drows, base, sort_bytes, s));
+    if (rows_mem == FX_MEM_HOST) HIP_TRY(hipMemcpyAsync(rows, drows, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    // (host buffers on either side: the call is done with them when it returns)
+    if (rows_mem == FX_MEM_HOST || ids_mem == FX_MEM_HOST) HIP_TRY(hipStreamSynchronize(s));
     return FX_OK;
 }
 
@@ -1779,7 +1939,36 @@ int fx_selector_create(FxIndex* h, int kind, const void* data, int64_t n, int da
     if (e == hipSuccess) e = hipMalloc((void**)&sel->cnt, sizeof(SelCounts));
     if (e == hipSuccess) e = hipHostMalloc((void**)&sel->pin, sizeof(SelCounts), hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&sel->ready, hipEventDisableTiming);
-    if (e == hipSuccess && kind == FX_SEL_RANGE) {
+    // a labelled index (fx_idmap.hip): ids, range bounds and bitmap bits mean labels
+    const int64_t* labels = h->has_ids ? h->labels : nullptr;
+    if (e == hipSuccess && labels && nt > 0) {
+        if (kind == FX_SEL_RANGE) {
+            e = launch_sel_range_lbl(labels, imin, imax, nt, invert != 0, sel->mask, s);
+        } else {
+            const size_t bytes = (size_t)n * (kind == FX_SEL_IDS ? 8 : 1);
+            // index-owned scratch: [sort workspace of the id list | host data staged for the build]
+            size_t sort_bytes = 0;
+            if (kind == FX_SEL_IDS && n > 0) {
+                if (n > (int64_t)INT32_MAX) e = hipErrorInvalidValue;
+                else e = idmap_sort_bytes(n, false, &sort_bytes);
+            }
+            const bool stage = data_mem == FX_MEM_HOST && n > 0;
+            if (e == hipSuccess && sort_bytes + (stage ? bytes : 0) > 0)
+                e = h->idm_ws.ensure(sort_bytes + (stage ? bytes : 0));
+            const void* dev = data;
+            if (e == hipSuccess && stage) {
+                dev = (char*)h->idm_ws.p + sort_bytes;
+                e = hipMemcpyAsync((void*)dev, data, bytes, hipMemcpyHostToDevice, s);
+            }
+            if (e == hipSuccess)
+                e = kind == FX_SEL_IDS
+                        ? launch_sel_ids_lbl(labels, (const int64_t*)dev, n, nt, invert != 0, sel->mask, h->idm_ws.p,
+                                             sort_bytes, s)
+                        : launch_sel_bitmap_lbl(labels, (const uint8_t*)dev, n, nt, invert != 0, sel->mask, s);
+            // (host data: the pageable copy above has to be out of the caller's array before the call returns)
+            if (e == hipSuccess && stage) e = hipStreamSynchronize(s);
+        }
+    } else if (e == hipSuccess && kind == FX_SEL_RANGE) {
         // ids -> local rows, clamped to the index (id_offset >= 0; differences of int64 ids may not overflow)
         auto local = [&](int64_t id) { return id <= off ? (int64_t)0 : std::min(id - off, nt); };
         e = launch_sel_range(local(imin), local(imax), nt, invert != 0, sel->mask, s);
@@ -2091,6 +2280,7 @@ int fx_index_range_search(FxIndex* h, int64_t nq, const void* q, int q_dtype, in
     f.nq = nq;
     f.radius = radius;
     f.id_offset = h->id_offset;
+    f.labels = h->has_ids ? h->labels : nullptr;
     f.dist = (float*)h->rg_dist.p;
     f.sorted = (uint64_t*)h->rg_sorted.p;
     f.temp = h->rg_temp.p;
@@ -2145,6 +2335,7 @@ int fx_index_reset(FxIndex* h) {
         HIP_TRY(hipMemsetD32((hipDeviceptr_t)h->norms, 0x7f800000u, (size_t)h->cap_rows));
     }
     h->ntotal = 0;
+    h->has_ids = false;  // the next add decides the mode again (the label buffer stays allocated)
     ++h->epoch;
     h->img_rows = 0;
     h->mu_rows = 0;
@@ -2171,17 +2362,33 @@ int fx_index_reconstruct_n(FxIndex* h, int64_t i0, int64_t n, float* out) {
     return FX_OK;
 }
 
+// the header fields an IxF2 file and an IxM2 / IxMp wrapper share, after the fourcc
+static bool write_index_header(FILE* f, int32_t d, int64_t nt) {
+    const int32_t metric = FX_METRIC_L2;
+    const int64_t dummy = 1 << 20;
+    const uint8_t trained = 1;
+    return fwrite(&d, 4, 1, f) == 1 && fwrite(&nt, 8, 1, f) == 1 && fwrite(&dummy, 8, 1, f) == 1 &&
+           fwrite(&dummy, 8, 1, f) == 1 && fwrite(&trained, 1, 1, f) == 1 && fwrite(&metric, 4, 1, f) == 1;
+}
+static bool read_index_header(FILE* f, int32_t* d, int64_t* nt, int32_t* metric) {
+    int64_t d1 = 0, d2 = 0;
+    uint8_t trained = 0;
+    return fread(d, 4, 1, f) == 1 && fread(nt, 8, 1, f) == 1 && fread(&d1, 8, 1, f) == 1 && fread(&d2, 8, 1, f) == 1 &&
+           fread(&trained, 1, 1, f) == 1 && fread(metric, 4, 1, f) == 1;
+}
+
 int fx_index_write(FxIndex* h, const char* path) {
     if (!h || !path) return set_err(FX_E_ARG, "null argument");
     if (h->metric != FX_METRIC_L2) return set_err(FX_E_UNSUPPORTED, "IxF2 writer supports METRIC_L2 only");
     FILE* f = fopen(path, "wb");
     if (!f) return set_err(FX_E_IO, "cannot open %s for writing", path);
-    const int32_t d = h->d, metric = FX_METRIC_L2;
-    const int64_t nt = h->ntotal, dummy = 1 << 20, count = h->ntotal * (int64_t)h->d;
-    const uint8_t trained = 1;
-    bool ok = fwrite("IxF2", 1, 4, f) == 4 && fwrite(&d, 4, 1, f) == 1 && fwrite(&nt, 8, 1, f) == 1 &&
-              fwrite(&dummy, 8, 1, f) == 1 && fwrite(&dummy, 8, 1, f) == 1 && fwrite(&trained, 1, 1, f) == 1 &&
-              fwrite(&metric, 4, 1, f) == 1 && fwrite(&count, 8, 1, f) == 1;
+    const int32_t d = h->d;
+    const int64_t nt = h->ntotal, count = h->ntotal * (int64_t)h->d;
+    const bool labelled = h->has_ids;
+    bool ok = true;
+    // a labelled index: faiss's IndexIDMap2 file -- its own header, the flat index as the sub-index, the labels
+    if (labelled) ok = fwrite("IxM2", 1, 4, f) == 4 && write_index_header(f, d, nt);
+    ok = ok && fwrite("IxF2", 1, 4, f) == 4 && write_index_header(f, d, nt) && fwrite(&count, 8, 1, f) == 1;
     const int64_t chunk = std::max<int64_t>(1, (64ll << 20) / ((int64_t)h->d * 4));
     std::vector<float> buf;
     for (int64_t r0 = 0; ok && r0 < nt; r0 += chunk) {
@@ -2193,6 +2400,15 @@ int fx_index_write(FxIndex* h, const char* path) {
             return rc;
         }
         ok = fwrite(buf.data(), 4, buf.size(), f) == buf.size();
+    }
+    if (ok && labelled) {
+        std::vector<int64_t> ids((size_t)nt);
+        const int rc = fx_index_get_ids(h, 0, nt, ids.data(), FX_MEM_HOST);
+        if (rc != FX_OK) {
+            fclose(f);
+            return rc;
+        }
+        ok = fwrite(&nt, 8, 1, f) == 1 && fwrite(ids.data(), 8, ids.size(), f) == ids.size();
     }
     if (fclose(f) != 0) ok = false;
     if (!ok) return set_err(FX_E_IO, "short write to %s", path);
@@ -2206,20 +2422,24 @@ int fx_index_read(const char* path, int storage_dtype, int device, FxIndex** out
     if (!f) return set_err(FX_E_IO, "could not open %s for reading", path);
     char fourcc[4];
     int32_t d = 0, metric = 0;
-    int64_t nt = 0, d1 = 0, d2 = 0, count = 0;
-    uint8_t trained = 0;
-    bool ok = fread(fourcc, 1, 4, f) == 4 && fread(&d, 4, 1, f) == 1 && fread(&nt, 8, 1, f) == 1 &&
-              fread(&d1, 8, 1, f) == 1 && fread(&d2, 8, 1, f) == 1 && fread(&trained, 1, 1, f) == 1 &&
-              fread(&metric, 4, 1, f) == 1 && fread(&count, 8, 1, f) == 1;
+    int64_t nt = 0, count = 0;
+    bool ok = fread(fourcc, 1, 4, f) == 4;
+    // IndexIDMap ("IxMp") / IndexIDMap2 ("IxM2"): a header of their own around the flat sub-index
+    const bool labelled = ok && (memcmp(fourcc, "IxM2", 4) == 0 || memcmp(fourcc, "IxMp", 4) == 0);
+    int32_t wd = 0, wmetric = 0;
+    int64_t wnt = 0;
+    if (labelled) ok = read_index_header(f, &wd, &wnt, &wmetric) && fread(fourcc, 1, 4, f) == 4;
+    ok = ok && read_index_header(f, &d, &nt, &metric) && fread(&count, 8, 1, f) == 1;
     if (!ok) {
         fclose(f);
         return set_err(FX_E_IO, "%s: truncated IxF2 header", path);
     }
     if (memcmp(fourcc, "IxF2", 4) != 0) {
         fclose(f);
-        return set_err(FX_E_IO, "%s: unsupported index fourcc (only IxF2 / IndexFlatL2)", path);
+        return set_err(FX_E_IO, "%s: unsupported index fourcc (only IxF2 / IndexFlatL2, alone or inside IxMp / IxM2)", path);
     }
-    if (d <= 0 || nt < 0 || metric != FX_METRIC_L2 || count != nt * (int64_t)d) {
+    if (d <= 0 || nt < 0 || metric != FX_METRIC_L2 || count != nt * (int64_t)d ||
+        (labelled && (wd != d || wnt != nt || wmetric != metric))) {
         fclose(f);
         return set_err(FX_E_IO, "%s: inconsistent IxF2 header", path);
     }
@@ -2240,6 +2460,26 @@ int fx_index_read(const char* path, int storage_dtype, int device, FxIndex** out
             break;
         }
         rc = fx_index_add(h, nr, buf.data(), FX_F32, FX_MEM_HOST);
+    }
+    if (rc == FX_OK && labelled) {
+        // i64 n, n labels: attached to the rows just added (the index becomes a labelled one)
+        int64_t n = -1;
+        std::vector<int64_t> ids;
+        if (fread(&n, 8, 1, f) != 1 || n != nt) {
+            rc = set_err(FX_E_IO, "%s: truncated or inconsistent id map (%lld ids for %lld rows)", path, (long long)n,
+                         (long long)nt);
+        } else {
+            ids.resize((size_t)n);
+            if (n > 0 && fread(ids.data(), 8, ids.size(), f) != ids.size()) rc = set_err(FX_E_IO, "%s: truncated id map", path);
+        }
+        if (rc == FX_OK) {
+            std::lock_guard<std::mutex> lk(h->mu);
+            DeviceGuard g(h->device);
+            h->has_ids = true;
+            hipError_t e = grow_labels(h);
+            if (e == hipSuccess && n > 0) e = hipMemcpy(h->labels, ids.data(), (size_t)n * 8, hipMemcpyHostToDevice);
+            if (e != hipSuccess) rc = set_err(FX_E_HIP, "%s: storing the id map: %s", path, hipGetErrorString(e));
+        }
     }
     fclose(f);
     if (rc != FX_OK) {

@@ -1,5 +1,5 @@
 // fx_internal.h -- shared between the HIP translation units (fx_kernels.hip,
-// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip) and the host C ABI
+// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip) and the host C ABI
 // (fx_index.cpp): tiling constants, kernel parameter blocks, the launchers'
 // prototypes and their host-side helpers.  Not part of the public ABI
 // (include/fx_index.h).
@@ -118,6 +118,7 @@ struct RefineParams {
                            // 2 rho sqrt(D) for a row at exact distance D (L2, 16-bit / fp32 rows)
     const double* qshift;  // [nq] s_q: approx key + s_q estimates the exact distance
     int64_t id_offset;
+    const int64_t* labels; // non-null (a labelled index, fx_idmap.hip): I = labels[row]; null: row + id_offset
     float* D;              // [nq][k]
     int64_t* I;
     int* n_flag;           // uncertified counter
@@ -262,7 +263,8 @@ constexpr int V5_TR = 64;
 hipError_t launch_exact_fallback(int st_dt, int metric, const char* codes, int row_bytes, int kdim,
                                  int64_t ntotal, const float* qf32, const int* n_flag, int k,
                                  int64_t id_offset, float* cand_d, int* cand_i, float* D, int64_t* I,
-                                 hipStream_t s, const uint32_t* row_mask = nullptr);
+                                 hipStream_t s, const uint32_t* row_mask = nullptr,
+                                 const int64_t* labels = nullptr);
 hipError_t launch_merge_shards(int metric, int nshards, int64_t nq, int k, const float* D_in,
                                const int64_t* I_in, float* D_out, int64_t* I_out, hipStream_t s);
 // k > FX_BIG_K (fx_hugek.hip): exact key of every (query, row) pair, a radix
@@ -276,6 +278,7 @@ struct HugeKParams {
     int64_t nq;
     int k;
     int64_t id_offset;
+    const int64_t* labels; // non-null: I = labels[row] (null: row + id_offset)
     float* D;              // [nq][k] on the device
     int64_t* I;
 };
@@ -310,6 +313,7 @@ struct RangeFinish {
     int64_t nq;
     float radius;
     int64_t id_offset;
+    const int64_t* labels; // non-null: I = labels[row] (null: row + id_offset)
     float* dist;           // [n] scratch: exact distance of words[i]
     uint64_t* sorted;      // [n] scratch: words in (query, row) order, sentinels last
     void* temp;            // rocPRIM temporaries (range_sort_temp_bytes)
@@ -369,6 +373,32 @@ hipError_t launch_keep_prefix(const uint32_t* mask, int64_t ntotal, unsigned* pr
 hipError_t launch_move_rows(const char* codes, const float* norms, const uint32_t* mask, const unsigned* prefix,
                             int64_t ntotal, int row_bytes, int64_t s0, int64_t s1, char* dst_codes, float* dst_norms,
                             int64_t dbase, hipStream_t s);
+// stable external ids (fx_idmap.hip): a labelled index carries one int64 label
+// per row (FxIndex::labels); these are the label -> row direction.
+// Selector masks by label over rows [0, ntotal): a row is selected iff its
+// label is a member (invert: the complement within the rows); each writes
+// every word of the mask.
+//   range:  imin <= label < imax
+//   bitmap: (uint64_t)label >> 3 < nbytes and the label's bit set (negative labels: never)
+//   ids:    label in ids[0, n) -- ids is sorted on the device first, into
+//           ws (idmap_sort_bytes(n, false) bytes), then every row binary-searches it
+hipError_t launch_sel_range_lbl(const int64_t* labels, int64_t imin, int64_t imax, int64_t ntotal, int invert,
+                                uint32_t* mask, hipStream_t s);
+hipError_t launch_sel_bitmap_lbl(const int64_t* labels, const uint8_t* bits, int64_t nbytes, int64_t ntotal,
+                                 int invert, uint32_t* mask, hipStream_t s);
+hipError_t idmap_sort_bytes(int64_t n, bool pairs, size_t* bytes);
+hipError_t launch_sel_ids_lbl(const int64_t* labels, const int64_t* ids, int64_t n, int64_t ntotal, int invert,
+                              uint32_t* mask, void* ws, size_t ws_bytes, hipStream_t s);
+// rows[i] <- the LAST row whose label is ids[i], -1 when none (n <= INT_MAX;
+// ws: idmap_sort_bytes(n, true) bytes): the (id, position) pairs sorted, every
+// row's label binary-searched, atomicMax of the row into the id's first sorted
+// slot, then the runs' answers scattered back to input order
+hipError_t launch_rows_of_labels(const int64_t* labels, int64_t ntotal, const int64_t* ids, int64_t n, int64_t* rows,
+                                 void* ws, size_t ws_bytes, hipStream_t s);
+// remove_ids: dst[prefix(r)] <- labels[r] for the rows r the mask keeps (a set
+// bit: removed), out of place (prefix: launch_keep_prefix's words)
+hipError_t launch_compact_labels(const int64_t* labels, const uint32_t* mask, const unsigned* prefix, int64_t ntotal,
+                                 int64_t* dst, hipStream_t s);
 // bits[0] <- max(bits[0], float bits of the largest of norms[0, n)) (atomicMax)
 hipError_t launch_norm_max(const float* norms, int64_t n, unsigned* bits, hipStream_t s);
 // fp32 code rows [r0, r1) -> their F32S scan image (same row stride)

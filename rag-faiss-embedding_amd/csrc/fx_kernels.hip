@@ -871,7 +871,7 @@ __global__ __launch_bounds__(256) void k_refine(RefineParams p) {
     if (lane < p.k) {
         const bool valid = id != INT_MAX;
         p.D[q * p.k + lane] = valid ? (METRIC == L2 ? key : -key) : (METRIC == L2 ? FLT_MAX : -FLT_MAX);
-        p.I[q * p.k + lane] = valid ? (int64_t)id + p.id_offset : (int64_t)-1;
+        p.I[q * p.k + lane] = valid ? result_id(p.labels, id, p.id_offset) : (int64_t)-1;
     }
     // Rows the selection dropped all have approx key >= td (DESIGN.md
     // "certification"); they cannot outrank the k-th result when
@@ -1050,7 +1050,7 @@ __global__ __launch_bounds__(64 * NW) void k_refine_wg(RefineParams p) {
     if (lane < p.k) {
         const bool valid = id != INT_MAX;
         p.D[q * p.k + lane] = valid ? (METRIC == L2 ? key : -key) : (METRIC == L2 ? FLT_MAX : -FLT_MAX);
-        p.I[q * p.k + lane] = valid ? (int64_t)id + p.id_offset : (int64_t)-1;
+        p.I[q * p.k + lane] = valid ? result_id(p.labels, id, p.id_offset) : (int64_t)-1;
     }
     if (nvalid >= KP || gq < 0xff800000u) {  // (k_refine: certify when anything pruned)
         const float kth = __shfl(key, p.k - 1, 64);
@@ -1145,7 +1145,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_refine_big(RefineParams p) {
     for (int t = tid; t < p.k; t += BT_THREADS) {
         const bool valid = t < n1;
         p.D[oq * p.k + t] = valid ? (METRIC == L2 ? ed[t] : -ed[t]) : (METRIC == L2 ? FLT_MAX : -FLT_MAX);
-        p.I[oq * p.k + t] = valid ? (int64_t)ei[t] + p.id_offset : (int64_t)-1;
+        p.I[oq * p.k + t] = valid ? result_id(p.labels, ei[t], p.id_offset) : (int64_t)-1;
     }
     if (tid == 0) {
         bool ok;
@@ -1214,8 +1214,8 @@ __global__ __launch_bounds__(BT_THREADS) void k_fb_scan(const char* __restrict__
 template <int METRIC>
 __global__ __launch_bounds__(BT_THREADS) void k_fb_merge(const int* __restrict__ n_flag, int64_t ntotal, int k,
                                                          const float* __restrict__ cd, const int* __restrict__ ci,
-                                                         int64_t id_offset, float* __restrict__ D,
-                                                         int64_t* __restrict__ I) {
+                                                         int64_t id_offset, const int64_t* __restrict__ labels,
+                                                         float* __restrict__ D, int64_t* __restrict__ I) {
     __shared__ float sd[BT_MAXB];
     __shared__ int si[BT_MAXB];
     __shared__ BtState<int> st;
@@ -1238,7 +1238,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_fb_merge(const int* __restrict__
         for (int t = threadIdx.x; t < k; t += BT_THREADS) {
             const bool valid = t < c;
             D[q * k + t] = valid ? (METRIC == L2 ? sd[t] : -sd[t]) : (METRIC == L2 ? FLT_MAX : -FLT_MAX);
-            I[q * k + t] = valid ? (int64_t)si[t] + id_offset : (int64_t)-1;
+            I[q * k + t] = valid ? result_id(labels, si[t], id_offset) : (int64_t)-1;
         }
         __syncthreads();
     }
@@ -1470,7 +1470,8 @@ hipError_t launch_refine(int st_dt, int metric, const RefineParams& p, hipStream
 
 hipError_t launch_exact_fallback(int st_dt, int metric, const char* codes, int row_bytes, int kdim, int64_t ntotal,
                                  const float* qf32, const int* n_flag, int k, int64_t id_offset, float* cand_d,
-                                 int* cand_i, float* D, int64_t* I, hipStream_t s, const uint32_t* row_mask) {
+                                 int* cand_i, float* D, int64_t* I, hipStream_t s, const uint32_t* row_mask,
+                                 const int64_t* labels) {
     hipError_t e = dispatch_dt_metric<DT_STORED>(st_dt, metric, [&](auto dt, auto mt) {
         hipLaunchKernelGGL((k_fb_scan<dt(), mt()>), dim3(FB_SCAN_GRID), dim3(BT_THREADS), 0, s, codes, row_bytes, kdim,
                            ntotal, qf32, n_flag, k, cand_d, cand_i, row_mask);
@@ -1479,10 +1480,10 @@ hipError_t launch_exact_fallback(int st_dt, int metric, const char* codes, int r
     if (e != hipSuccess) return e;
     if (metric == L2)
         hipLaunchKernelGGL(k_fb_merge<L2>, dim3(FB_MERGE_GRID), dim3(BT_THREADS), 0, s, n_flag, ntotal, k, cand_d,
-                           cand_i, id_offset, D, I);
+                           cand_i, id_offset, labels, D, I);
     else
         hipLaunchKernelGGL(k_fb_merge<IP>, dim3(FB_MERGE_GRID), dim3(BT_THREADS), 0, s, n_flag, ntotal, k, cand_d,
-                           cand_i, id_offset, D, I);
+                           cand_i, id_offset, labels, D, I);
     return hipGetLastError();
 }
 

@@ -33,7 +33,7 @@
 //                   32 and the query's): the survivors in (query, row) order
 //                   in front of the sentinels.
 //   k_range_lims    lims[q] = first sorted word of query q (binary search).
-//   k_range_ids     I = row + id_offset.
+//   k_range_ids     I = row + id_offset (a labelled index: the row's label).
 #include "fx_device.h"
 
 #include <hipcub/hipcub.hpp>
@@ -166,10 +166,11 @@ __global__ __launch_bounds__(RG_THREADS) void k_range_lims(const unsigned long l
 
 __global__ __launch_bounds__(RG_THREADS) void k_range_ids(const unsigned long long* __restrict__ sorted,
                                                           const int64_t* __restrict__ lims, int64_t nq,
-                                                          int64_t id_offset, int64_t* __restrict__ I) {
+                                                          int64_t id_offset, const int64_t* __restrict__ labels,
+                                                          int64_t* __restrict__ I) {
     const int64_t total = lims[nq];
     for (int64_t i = (int64_t)blockIdx.x * RG_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * RG_THREADS)
-        I[i] = (int64_t)(sorted[i] & 0xffffffffull) + id_offset;
+        I[i] = result_id(labels, (int64_t)(sorted[i] & 0xffffffffull), id_offset);
 }
 
 namespace {
@@ -227,7 +228,7 @@ hipError_t launch_range_finish(const RangeFinish& f, hipStream_t s) {
     hipLaunchKernelGGL(k_range_lims, dim3(rg_blocks(f.nq + 1)), dim3(RG_THREADS), 0, s,
                        (const unsigned long long*)f.sorted, f.n, f.nq, f.lims);
     hipLaunchKernelGGL(k_range_ids, dim3(std::min(rg_blocks(f.n), 4096u)), dim3(RG_THREADS), 0, s,
-                       (const unsigned long long*)f.sorted, (const int64_t*)f.lims, f.nq, f.id_offset, f.I);
+                       (const unsigned long long*)f.sorted, (const int64_t*)f.lims, f.nq, f.id_offset, f.labels, f.I);
     return hipGetLastError();
 }
 

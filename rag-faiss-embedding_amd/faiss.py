@@ -15,7 +15,13 @@ as faiss``:
   with ``IDSelectorRange``, ``IDSelectorArray``, ``IDSelectorBatch``,
   ``IDSelectorBitmap`` and ``IDSelectorNot``: only the selected ids are ranked
   (exactly: the scan itself skips the other rows);
-* ``write_index(index, path)`` / ``read_index(path)`` on the IxF2 format.
+* stable ids, ``IndexIDMap(index)`` / ``IndexIDMap2(index)`` with
+  ``add_with_ids(x, ids)``, ``id_map`` and (``IndexIDMap2``)
+  ``reconstruct(id)``: every row carries a caller-chosen int64 label that
+  ``search`` / ``range_search`` return, selectors and ``remove_ids`` speak,
+  and removals leave intact;
+* ``write_index(index, path)`` / ``read_index(path)`` on the IxF2 format
+  (IxM2 for a labelled index).
 
 Inputs may be numpy arrays (as in the reference: host fp32, results returned
 as numpy) or torch tensors already resident on the GPU (fp32/bf16/fp16;
@@ -71,7 +77,8 @@ def _tensor_dtype(x) -> int:
 # ---------------------------------------------------------------------------
 class IDSelector:
     """A set of ids a search is restricted to.  Ids are the ids ``search``
-    returns (row + the index's id offset).  The device image a search needs
+    returns (row + the index's id offset; on a labelled index -- ``IndexIDMap``
+    -- the rows' labels).  The device image a search needs
     (``FxSelector``: row mask + live tiles) is built on first use and cached
     per index for the index's current ``ntotal`` and id offset; after ``add``
     / ``reset`` / ``remove_ids`` it is rebuilt transparently."""
@@ -116,6 +123,7 @@ class IDSelector:
     def stats(self, index: "_FlatIndex") -> dict:
         """Of this selector on ``index``: selected ``rows`` and live 128-row
         ``tiles`` (the tiles the filtered scan visits)."""
+        index = _flat(index)
         index._bind_stream(_is_device_tensor(self._spec()[1]))
         r, t = ctypes.c_int64(0), ctypes.c_int64(0)
         index._check(index._lib.fx_selector_stats(self._handle(index), ctypes.byref(r), ctypes.byref(t)))
@@ -308,6 +316,69 @@ class _FlatIndex:
         self._bind_stream(False)
         self._check(self._lib.fx_index_add(self._h, x.shape[0], x.ctypes.data_as(ctypes.c_void_p), _lib.F32,
                                            _lib.MEM_HOST))
+
+    def add_with_ids(self, x, ids) -> None:
+        """``fx_index_add_with_ids``: append the rows of ``x``, row i labelled
+        ``ids[i]`` (int64).  The thin binding ``IndexIDMap`` / ``IndexIDMap2``
+        call; the first one into an empty index turns its labelled mode on."""
+        dev_ids = _is_device_tensor(ids)
+        ids = _id_array(ids)
+        n_ids = int(ids.numel()) if dev_ids else int(ids.size)
+        if dev_ids:
+            assert ids.device.index == self.device, f"ids on cuda:{ids.device.index}, index on cuda:{self.device}"
+            iptr, imem = ctypes.c_void_p(ids.data_ptr()), _lib.MEM_DEVICE
+        else:
+            iptr, imem = ctypes.c_void_p(ids.ctypes.data), _lib.MEM_HOST
+        if _is_device_tensor(x):
+            assert x.dim() == 2 and x.shape[1] == self.d, "dimension mismatch"
+            assert x.device.index == self.device, f"tensor on cuda:{x.device.index}, index on cuda:{self.device}"
+            assert n_ids == x.shape[0], f"add_with_ids: {n_ids} ids for {x.shape[0]} rows"
+            x = x.contiguous()
+            self._bind_stream(True)
+            self._check(self._lib.fx_index_add_with_ids(self._h, x.shape[0], ctypes.c_void_p(x.data_ptr()),
+                                                        _tensor_dtype(x), _lib.MEM_DEVICE, iptr, imem))
+            return
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        assert x.ndim == 2 and x.shape[1] == self.d, "dimension mismatch"
+        assert n_ids == x.shape[0], f"add_with_ids: {n_ids} ids for {x.shape[0]} rows"
+        self._bind_stream(dev_ids)
+        self._check(self._lib.fx_index_add_with_ids(self._h, x.shape[0], x.ctypes.data_as(ctypes.c_void_p), _lib.F32,
+                                                    _lib.MEM_HOST, iptr, imem))
+
+    @property
+    def has_ids(self) -> bool:
+        """True while the index is in the labelled mode (``add_with_ids``)."""
+        v = ctypes.c_int(0)
+        self._check(self._lib.fx_index_has_ids(self._h, ctypes.byref(v)))
+        return bool(v.value)
+
+    def get_ids(self, i0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """The labels of rows ``[i0, i0 + n)`` (default: all) as numpy int64."""
+        n = self.ntotal - int(i0) if n is None else int(n)
+        out = np.empty(max(n, 0), dtype=np.int64)
+        self._check(self._lib.fx_index_get_ids(self._h, int(i0), n, out.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST))
+        return out
+
+    def rows_of_ids(self, ids):
+        """``fx_index_rows_of_ids``: for every label of ``ids`` the last row
+        that carries it, -1 when none.  numpy in -> numpy out; an int64 tensor
+        on the index's GPU in -> a device tensor out (stream-ordered)."""
+        if _is_device_tensor(ids):
+            t = _torch()
+            ids = _id_array(ids)
+            assert ids.device.index == self.device, f"ids on cuda:{ids.device.index}, index on cuda:{self.device}"
+            rows = t.empty_like(ids)
+            self._bind_stream(True)
+            self._check(self._lib.fx_index_rows_of_ids(self._h, ctypes.c_void_p(ids.data_ptr()), int(ids.numel()),
+                                                       _lib.MEM_DEVICE, ctypes.c_void_p(rows.data_ptr()),
+                                                       _lib.MEM_DEVICE))
+            return rows
+        ids = _id_array(ids)
+        rows = np.empty(ids.size, dtype=np.int64)
+        self._bind_stream(False)
+        self._check(self._lib.fx_index_rows_of_ids(self._h, ids.ctypes.data_as(ctypes.c_void_p), int(ids.size),
+                                                   _lib.MEM_HOST, rows.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST))
+        return rows
 
     def search(self, x, k: int, *, params=None, D=None, I=None) -> Tuple:
         """``IndexFlat.search`` (faiss_store.py:64): k nearest rows of every
@@ -521,17 +592,106 @@ class IndexFlatIP(_FlatIndex):
     metric_type = METRIC_INNER_PRODUCT
 
 
-def write_index(index: _FlatIndex, path: str) -> None:
-    """``faiss.write_index`` (faiss_store.py:91): IxF2 file, fp32 codes."""
+class IndexIDMap:
+    """``faiss.IndexIDMap(index)``: stable caller-chosen int64 ids over an
+    ``IndexFlatL2`` / ``IndexFlatIP`` of this module, which must be empty
+    ("index must be empty on input").  ``add_with_ids(x, ids)`` labels every
+    row; ``search`` / ``range_search`` return the labels, selectors
+    (``IDSelectorRange`` / ``Batch`` / ``Bitmap`` / ``Not``) and ``remove_ids``
+    speak them, and they survive removals (the label array is compacted with
+    the rows on the GPU).  Labels are any int64 -- negative, above 2^32,
+    duplicated (one document id on all its chunk rows); -1 is legal but looks
+    like the "missing slot" marker in results.  Results rank by (distance,
+    row): ties break on insertion order, not on label.
+
+    Unlike faiss, the labels live in the wrapped index's own C object, not in
+    this wrapper: once labelled, ``self.index`` itself returns labels too (in
+    faiss the inner index keeps returning row numbers)."""
+
+    def __init__(self, index):
+        if index.ntotal != 0:
+            raise AssertionError("index must be empty on input")
+        self.index = index
+
+    @classmethod
+    def _wrap(cls, index):
+        """Around an index that is labelled already (``read_index``)."""
+        self = cls.__new__(cls)
+        self.index = index
+        return self
+
+    d = property(lambda self: self.index.d)
+    ntotal = property(lambda self: self.index.ntotal)
+    metric_type = property(lambda self: self.index.metric_type)
+    is_trained = property(lambda self: self.index.is_trained)
+
+    def add_with_ids(self, x, ids) -> None:
+        """``IndexIDMap.add_with_ids``: numpy rows and ids, or device tensors
+        (fp32 / bf16 / fp16 rows, int64 ids: stream-ordered)."""
+        self.index.add_with_ids(x, ids)
+
+    def add(self, x) -> None:
+        raise RuntimeError("add does not make sense with IndexIDMap: use add_with_ids")
+
+    def search(self, x, k: int, *, params=None, D=None, I=None) -> Tuple:
+        """``search`` of the wrapped index; ``I`` holds labels (-1: missing)."""
+        return self.index.search(x, k, params=params, D=D, I=I)
+
+    def range_search(self, x, radius: float, *, params=None) -> Tuple:
+        """``range_search`` of the wrapped index; ``I`` holds labels, ordered by
+        ascending ROW within a query."""
+        return self.index.range_search(x, radius, params=params)
+
+    def remove_ids(self, x) -> int:
+        """Remove every row whose label ``x`` selects (an ``IDSelector``, or
+        labels as ``IDSelectorBatch`` takes them); returns the rows removed."""
+        return self.index.remove_ids(x)  # (bumps the wrapped index's _resets: built selectors are stale)
+
+    def reset(self) -> None:
+        self.index.reset()  # (... and so does this)
+
+    @property
+    def id_map(self) -> np.ndarray:
+        """``IndexIDMap.id_map``: the label of every row, numpy int64 (a
+        read-back from the device)."""
+        if self.index.ntotal == 0:
+            return np.empty(0, dtype=np.int64)
+        return self.index.get_ids()
+
+
+class IndexIDMap2(IndexIDMap):
+    """``faiss.IndexIDMap2``: ``IndexIDMap`` plus ``reconstruct(id)``."""
+
+    def reconstruct(self, key: int) -> np.ndarray:
+        """The stored vector of label ``key`` (of the last row added with it,
+        as ``IndexIDMap2.rev_map`` keeps); an unknown label raises
+        ``RuntimeError``."""
+        row = int(self.index.rows_of_ids(np.array([int(key)], dtype=np.int64))[0])
+        if row < 0:
+            raise RuntimeError(f"reconstruct: key {int(key)} not found")
+        return self.index.reconstruct_n(row, 1)[0]
+
+
+def _flat(index):
+    """The flat index behind ``index`` (an ``IndexIDMap`` wraps one)."""
+    return index.index if isinstance(index, IndexIDMap) else index
+
+
+def write_index(index, path: str) -> None:
+    """``faiss.write_index`` (faiss_store.py:91): IxF2 file, fp32 codes; a
+    labelled index (``IndexIDMap`` / ``IndexIDMap2``) as an IxM2 file."""
+    index = _flat(index)
     check(index._lib.fx_index_write(index._h, str(path).encode()), index._lib)
 
 
-def read_index(path: str, dtype: str = "float32", device: int = 0) -> IndexFlatL2:
-    """``faiss.read_index`` (faiss_store.py:106): IxF2 file -> HBM index."""
+def read_index(path: str, dtype: str = "float32", device: int = 0):
+    """``faiss.read_index`` (faiss_store.py:106): IxF2 file -> HBM
+    ``IndexFlatL2``; an IxMp / IxM2 file -> ``IndexIDMap2`` around one."""
     h = ctypes.c_void_p()
     rc = lib.fx_index_read(str(path).encode(), _DTYPES[dtype], int(device), ctypes.byref(h))
     check(rc)
-    return IndexFlatL2(0, dtype=dtype, device=device, _handle=h)
+    flat = IndexFlatL2(0, dtype=dtype, device=device, _handle=h)
+    return IndexIDMap2._wrap(flat) if flat.has_ids else flat
 
 
 def synth_fill(out, row0: int, seed: int) -> None:

@@ -1,0 +1,326 @@
+// idmap_check.cpp -- host-sanitizer driver of the stable-id calls of the C ABI
+// (include/fx_index.h, "stable ids").
+//
+// Built by `make -C rag-faiss-embedding_amd/csrc asan` next to abi_check, with
+// the host C++ of fx_index.cpp under -fsanitize=address,undefined, and run on
+// the GPU box by tests/test_idmap_native.py.  It walks fx_index_add_with_ids
+// (ragged growth, host and device ids), fx_index_has_ids, fx_index_get_ids,
+// fx_index_rows_of_ids, the mode rules, a labelled search / selector / removal,
+// and the IxM2 write / read including every truncation of the file.  Results
+// are checked against a brute force on the host; any mismatch or sanitizer
+// report ends the program with a non-zero status.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <random>
+#include <string>
+#include <vector>
+
+#include <unistd.h>
+
+#include "../../include/fx_index.h"
+
+static int g_fail = 0;
+#define CHECK(cond, ...)                                                   \
+    do {                                                                   \
+        if (!(cond)) {                                                     \
+            fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__);           \
+            fprintf(stderr, __VA_ARGS__);                                  \
+            fprintf(stderr, " (last error: %s)\n", fx_last_error());       \
+            ++g_fail;                                                      \
+        }                                                                  \
+    } while (0)
+#define OK(call) CHECK((call) == FX_OK, "%s", #call)
+
+// rows ranked by float64 squared L2 (ties -> smaller row), the first k
+static std::vector<int64_t> brute_rows(const std::vector<float>& xb, int64_t n, const float* q, int d, int k,
+                                       const std::vector<char>* allowed = nullptr) {
+    std::vector<std::pair<float, int64_t>> all;
+    for (int64_t r = 0; r < n; ++r) {
+        if (allowed && !(*allowed)[(size_t)r]) continue;
+        double s = 0;
+        for (int c = 0; c < d; ++c) {
+            const double t = (double)q[c] - (double)xb[r * d + c];
+            s += t * t;
+        }
+        all.push_back({(float)s, r});
+    }
+    std::sort(all.begin(), all.end());
+    std::vector<int64_t> out((size_t)k, -1);
+    for (int j = 0; j < k && j < (int)all.size(); ++j) out[(size_t)j] = all[(size_t)j].second;
+    return out;
+}
+
+static std::vector<char> slurp(const std::string& path) {
+    std::vector<char> b;
+    if (FILE* f = fopen(path.c_str(), "rb")) {
+        fseek(f, 0, SEEK_END);
+        b.resize((size_t)ftell(f));
+        fseek(f, 0, SEEK_SET);
+        if (fread(b.data(), 1, b.size(), f) != b.size()) b.clear();
+        fclose(f);
+    }
+    return b;
+}
+
+static void spill(const std::string& path, const char* p, size_t n) {
+    if (FILE* f = fopen(path.c_str(), "wb")) {
+        fwrite(p, 1, n, f);
+        fclose(f);
+    }
+}
+
+int main() {
+    int ndev = 0;
+    OK(fx_device_count(&ndev));
+    if (ndev == 0) {
+        fprintf(stderr, "no GPU visible\n");
+        return 2;
+    }
+    std::mt19937 rng(11);
+    std::normal_distribution<float> nd;
+    const int d = 48, k = 7;
+
+    // ---- argument errors without an index ----------------------------------
+    {
+        int has = 0;
+        int64_t one = 1;
+        float x[d] = {0};
+        CHECK(fx_index_add_with_ids(nullptr, 1, x, FX_F32, FX_MEM_HOST, &one, FX_MEM_HOST) == FX_E_ARG, "null index");
+        CHECK(fx_index_has_ids(nullptr, &has) == FX_E_ARG, "has_ids null index");
+        CHECK(fx_index_get_ids(nullptr, 0, 1, &one, FX_MEM_HOST) == FX_E_ARG, "get_ids null index");
+        CHECK(fx_index_rows_of_ids(nullptr, &one, 1, FX_MEM_HOST, &one, FX_MEM_HOST) == FX_E_ARG, "rows_of_ids null index");
+    }
+
+    FxIndex* ix = nullptr;
+    OK(fx_index_create(d, FX_F32, FX_METRIC_L2, 0, &ix));
+    int has = -1;
+    OK(fx_index_has_ids(ix, &has));
+    CHECK(has == 0, "a new index is labelled");
+    {
+        int64_t id = 5, row = 0;
+        float x[d] = {0};
+        CHECK(fx_index_add_with_ids(ix, -1, x, FX_F32, FX_MEM_HOST, &id, FX_MEM_HOST) == FX_E_ARG, "negative n");
+        CHECK(fx_index_add_with_ids(ix, 1, x, FX_F32, FX_MEM_HOST, nullptr, FX_MEM_HOST) == FX_E_ARG, "null ids");
+        CHECK(fx_index_add_with_ids(ix, 1, nullptr, FX_F32, FX_MEM_HOST, &id, FX_MEM_HOST) == FX_E_ARG, "null rows");
+        OK(fx_index_add_with_ids(ix, 0, nullptr, FX_F32, FX_MEM_HOST, nullptr, FX_MEM_HOST));
+        OK(fx_index_has_ids(ix, &has));
+        CHECK(has == 0, "n = 0 turned the mode on");
+        CHECK(fx_index_get_ids(ix, 0, 0, &id, FX_MEM_HOST) == FX_E_ARG, "get_ids without labels");
+        CHECK(fx_index_rows_of_ids(ix, &id, 1, FX_MEM_HOST, &row, FX_MEM_HOST) == FX_E_ARG, "rows_of_ids without labels");
+        OK(fx_index_set_id_offset(ix, 9));
+        CHECK(fx_index_add_with_ids(ix, 1, x, FX_F32, FX_MEM_HOST, &id, FX_MEM_HOST) == FX_E_ARG, "labels with an id offset");
+        OK(fx_index_set_id_offset(ix, 0));
+    }
+
+    // ---- ragged labelled growth, host and device ids -----------------------
+    std::vector<float> xb;
+    std::vector<int64_t> lab;
+    int64_t n = 0;
+    for (int64_t chunk : {1, 130, 700, 3, 1300}) {
+        std::vector<float> x((size_t)chunk * d);
+        for (auto& v : x) v = nd(rng);
+        std::vector<int64_t> ids((size_t)chunk);
+        for (int64_t i = 0; i < chunk; ++i) {
+            const int64_t r = n + i;
+            // every 5th row repeats an earlier label; negatives and values >= 2^40 among the rest
+            ids[(size_t)i] = r % 5 == 4 ? lab[(size_t)(r / 2)] : (r % 3 == 0 ? -(r + 2) : (1ll << 40) + 7 * r);
+            lab.push_back(ids[(size_t)i]);
+        }
+        if (chunk == 700) {  // device rows and ids: the stream-ordered form
+            float* dx = nullptr;
+            int64_t* di = nullptr;
+            CHECK(hipMalloc((void**)&dx, x.size() * 4) == hipSuccess, "hipMalloc");
+            CHECK(hipMalloc((void**)&di, ids.size() * 8) == hipSuccess, "hipMalloc");
+            CHECK(hipMemcpy(dx, x.data(), x.size() * 4, hipMemcpyHostToDevice) == hipSuccess, "hipMemcpy");
+            CHECK(hipMemcpy(di, ids.data(), ids.size() * 8, hipMemcpyHostToDevice) == hipSuccess, "hipMemcpy");
+            OK(fx_index_add_with_ids(ix, chunk, dx, FX_F32, FX_MEM_DEVICE, di, FX_MEM_DEVICE));
+            CHECK(hipDeviceSynchronize() == hipSuccess, "sync");
+            (void)hipFree(dx);
+            (void)hipFree(di);
+        } else {
+            OK(fx_index_add_with_ids(ix, chunk, x.data(), FX_F32, FX_MEM_HOST, ids.data(), FX_MEM_HOST));
+        }
+        xb.insert(xb.end(), x.begin(), x.end());
+        n += chunk;
+    }
+    OK(fx_index_has_ids(ix, &has));
+    CHECK(has == 1, "add_with_ids left the mode off");
+    {
+        float x[d] = {0};
+        CHECK(fx_index_add(ix, 1, x, FX_F32, FX_MEM_HOST) == FX_E_ARG, "plain add on a labelled index");
+        CHECK(fx_index_set_id_offset(ix, 4) == FX_E_ARG, "id offset on a labelled index");
+        OK(fx_index_set_id_offset(ix, 0));
+    }
+    // id_map: whole, a window, the empty window at the end, one past it
+    {
+        std::vector<int64_t> got((size_t)n, 0);
+        OK(fx_index_get_ids(ix, 0, n, got.data(), FX_MEM_HOST));
+        CHECK(got == lab, "id_map differs from the labels added");
+        std::vector<int64_t> win(17, 0);
+        OK(fx_index_get_ids(ix, 125, 17, win.data(), FX_MEM_HOST));
+        CHECK(std::equal(win.begin(), win.end(), lab.begin() + 125), "id_map window");
+        OK(fx_index_get_ids(ix, n, 0, win.data(), FX_MEM_HOST));
+        CHECK(fx_index_get_ids(ix, n, 1, win.data(), FX_MEM_HOST) == FX_E_ARG, "id_map past the end");
+        CHECK(fx_index_get_ids(ix, -1, 1, win.data(), FX_MEM_HOST) == FX_E_ARG, "id_map negative start");
+    }
+
+    // ---- rows_of_ids: unique, duplicated (last row wins), unknown, repeated --
+    {
+        std::vector<int64_t> ask = {lab[0], lab[1], lab[(size_t)n - 1], 123456789, lab[1], lab[4], lab[400], 123456789};
+        std::vector<int64_t> rows(ask.size(), -7), want(ask.size(), -1);
+        for (size_t i = 0; i < ask.size(); ++i)
+            for (int64_t r = 0; r < n; ++r)
+                if (lab[(size_t)r] == ask[i]) want[i] = r;
+        OK(fx_index_rows_of_ids(ix, ask.data(), (int64_t)ask.size(), FX_MEM_HOST, rows.data(), FX_MEM_HOST));
+        CHECK(rows == want, "rows_of_ids differs from the host's last-row scan");
+        OK(fx_index_rows_of_ids(ix, nullptr, 0, FX_MEM_HOST, nullptr, FX_MEM_HOST));
+        CHECK(fx_index_rows_of_ids(ix, ask.data(), -1, FX_MEM_HOST, rows.data(), FX_MEM_HOST) == FX_E_ARG, "negative n");
+        CHECK(fx_index_rows_of_ids(ix, nullptr, 2, FX_MEM_HOST, rows.data(), FX_MEM_HOST) == FX_E_ARG, "null ids");
+    }
+
+    // ---- a labelled search, a selector by label, a removal by label ----------
+    std::vector<float> q((size_t)d);
+    for (auto& v : q) v = nd(rng);
+    auto search_check = [&](const std::vector<char>* allowed, FxSelector* sel, const char* what) {
+        std::vector<float> D((size_t)k);
+        std::vector<int64_t> I((size_t)k);
+        if (sel) OK(fx_index_search_sel(ix, sel, 1, q.data(), FX_F32, FX_MEM_HOST, k, D.data(), I.data(), FX_MEM_HOST));
+        else OK(fx_index_search(ix, 1, q.data(), FX_F32, FX_MEM_HOST, k, D.data(), I.data(), FX_MEM_HOST));
+        const std::vector<int64_t> rows = brute_rows(xb, n, q.data(), d, k, allowed);
+        for (int j = 0; j < k; ++j) {
+            const int64_t want = rows[(size_t)j] < 0 ? -1 : lab[(size_t)rows[(size_t)j]];
+            CHECK(I[(size_t)j] == want, "%s: slot %d holds %lld, expected label %lld", what, j, (long long)I[(size_t)j],
+                  (long long)want);
+        }
+    };
+    search_check(nullptr, nullptr, "labelled search");
+    {
+        // the labels of rows 3 .. 40, one of them twice, and an id no row carries
+        std::vector<int64_t> ids(lab.begin() + 3, lab.begin() + 41);
+        ids.push_back(lab[10]);
+        ids.push_back(987654321);
+        std::vector<char> allowed((size_t)n, 0);
+        int64_t count = 0;
+        for (int64_t r = 0; r < n; ++r)
+            if (std::find(ids.begin(), ids.end(), lab[(size_t)r]) != ids.end()) allowed[(size_t)r] = 1, ++count;
+        FxSelector* sel = nullptr;
+        OK(fx_selector_create(ix, FX_SEL_IDS, ids.data(), (int64_t)ids.size(), FX_MEM_HOST, 0, &sel));
+        int64_t rows = 0, tiles = 0;
+        OK(fx_selector_stats(sel, &rows, &tiles));
+        CHECK(rows == count, "selector by label: %lld rows, expected %lld", (long long)rows, (long long)count);
+        search_check(&allowed, sel, "search with a selector by label");
+        // remove them: the labels follow their rows
+        int64_t removed = 0;
+        OK(fx_index_remove_ids(ix, sel, &removed));
+        CHECK(removed == count, "remove_ids removed %lld rows, expected %lld", (long long)removed, (long long)count);
+        fx_selector_free(sel);
+        std::vector<float> xb2;
+        std::vector<int64_t> lab2;
+        for (int64_t r = 0; r < n; ++r)
+            if (!allowed[(size_t)r]) {
+                xb2.insert(xb2.end(), xb.begin() + r * d, xb.begin() + (r + 1) * d);
+                lab2.push_back(lab[(size_t)r]);
+            }
+        xb.swap(xb2);
+        lab.swap(lab2);
+        n = (int64_t)lab.size();
+        int64_t nt = 0;
+        OK(fx_index_ntotal(ix, &nt));
+        CHECK(nt == n, "ntotal after the removal");
+        std::vector<int64_t> got((size_t)n, 0);
+        OK(fx_index_get_ids(ix, 0, n, got.data(), FX_MEM_HOST));
+        CHECK(got == lab, "id_map after the removal");
+        search_check(nullptr, nullptr, "search after the removal");
+    }
+
+    // ---- IxM2 write / read, every truncation -------------------------------
+    {
+        const char* tmp = getenv("TMPDIR");
+        const std::string dir = tmp && *tmp ? tmp : "/tmp";
+        const std::string path = dir + "/fx_idmap_check_" + std::to_string((long)getpid()) + ".bin";
+        const std::string cut = path + ".cut";
+        OK(fx_index_write(ix, path.c_str()));
+        const std::vector<char> bytes = slurp(path);
+        const size_t flat = 4 + 33 + 8 + (size_t)n * d * 4;  // fourcc, header fields, count, codes
+        CHECK(bytes.size() == 4 + 33 + flat + 8 + (size_t)n * 8, "IxM2 file of %zu bytes", bytes.size());
+        CHECK(bytes.size() > 41 && memcmp(bytes.data(), "IxM2", 4) == 0 && memcmp(bytes.data() + 37, "IxF2", 4) == 0,
+              "IxM2 / IxF2 fourccs");
+        FxIndex* rd = nullptr;
+        OK(fx_index_read(path.c_str(), FX_F32, 0, &rd));
+        if (rd) {
+            int rhas = 0;
+            int64_t rnt = 0;
+            OK(fx_index_has_ids(rd, &rhas));
+            OK(fx_index_ntotal(rd, &rnt));
+            CHECK(rhas == 1 && rnt == n, "read back: has_ids %d, ntotal %lld", rhas, (long long)rnt);
+            std::vector<int64_t> got((size_t)n, 0);
+            OK(fx_index_get_ids(rd, 0, n, got.data(), FX_MEM_HOST));
+            CHECK(got == lab, "id_map of the index read back");
+            std::vector<float> D1((size_t)k), D2((size_t)k);
+            std::vector<int64_t> I1((size_t)k), I2((size_t)k);
+            OK(fx_index_search(ix, 1, q.data(), FX_F32, FX_MEM_HOST, k, D1.data(), I1.data(), FX_MEM_HOST));
+            OK(fx_index_search(rd, 1, q.data(), FX_F32, FX_MEM_HOST, k, D2.data(), I2.data(), FX_MEM_HOST));
+            CHECK(I1 == I2 && D1 == D2, "search of the index read back");
+            fx_index_free(rd);
+        }
+        // the same bytes under faiss's IndexIDMap fourcc
+        {
+            std::vector<char> mp = bytes;
+            memcpy(mp.data(), "IxMp", 4);
+            spill(cut, mp.data(), mp.size());
+            rd = nullptr;
+            OK(fx_index_read(cut.c_str(), FX_F32, 0, &rd));
+            int rhas = 0;
+            if (rd) OK(fx_index_has_ids(rd, &rhas));
+            CHECK(rhas == 1, "IxMp file read without labels");
+            fx_index_free(rd);
+        }
+        // cuts: inside either header, the codes, the id count and the id map, and one byte short
+        const size_t cuts[] = {0, 3, 4, 20, 36, 37, 40, 41, 60, 77, 80, 81, 85, 4 + 33 + flat - 1, 4 + 33 + flat,
+                               4 + 33 + flat + 7, 4 + 33 + flat + 8, 4 + 33 + flat + 8 + 17, bytes.size() - 1};
+        for (size_t c : cuts) {
+            if (c >= bytes.size()) continue;
+            spill(cut, bytes.data(), c);
+            rd = nullptr;
+            CHECK(fx_index_read(cut.c_str(), FX_F32, 0, &rd) == FX_E_IO && rd == nullptr, "truncated IxM2 file (%zu B) accepted", c);
+            if (rd) fx_index_free(rd);
+        }
+        // a foreign fourcc, outside and inside
+        for (size_t at : {(size_t)0, (size_t)37}) {
+            std::vector<char> f = bytes;
+            memcpy(f.data() + at, "XxF2", 4);
+            spill(cut, f.data(), f.size());
+            rd = nullptr;
+            CHECK(fx_index_read(cut.c_str(), FX_F32, 0, &rd) == FX_E_IO && rd == nullptr, "foreign fourcc at %zu accepted", at);
+            if (rd) fx_index_free(rd);
+        }
+        unlink(path.c_str());
+        unlink(cut.c_str());
+    }
+
+    // ---- reset clears the mode -------------------------------------------------
+    OK(fx_index_reset(ix));
+    OK(fx_index_has_ids(ix, &has));
+    CHECK(has == 0, "reset left the mode on");
+    {
+        std::vector<float> x((size_t)3 * d, 0.5f);
+        OK(fx_index_add(ix, 3, x.data(), FX_F32, FX_MEM_HOST));
+        int64_t ids[3] = {1, 2, 3};
+        CHECK(fx_index_add_with_ids(ix, 3, x.data(), FX_F32, FX_MEM_HOST, ids, FX_MEM_HOST) == FX_E_ARG,
+              "add_with_ids on an unlabelled index with rows");
+    }
+    fx_index_free(ix);
+
+    if (g_fail) fprintf(stderr, "idmap_check: %d failure(s)\n", g_fail);
+    else printf("idmap_check ok\n");
+    fflush(stdout);
+    fflush(stderr);
+    // skip static destructors, as abi_check does: the HIP runtime's own
+    // teardown frees memory through ASan's device allocator after the device
+    // runtime is unloaded (an ASan CHECK in ROCm code, not in this library)
+    _exit(g_fail ? 1 : 0);
+}
