@@ -28,6 +28,12 @@
  *     .id_map                                        faiss_IndexIDMap_id_map      fx_index_get_ids
  *     .reconstruct(id)                               faiss_Index_reconstruct      fx_index_rows_of_ids
  *                                                                                  + fx_index_reconstruct_n
+ *   index.reconstruct_    (the neighbours' vectors   faiss_Index_reconstruct_     fx_index_reconstruct_batch
+ *     batch(keys)          for MMR re-ranking; see    batch
+ *   index.search_and_      "stored vectors by key"   faiss_Index_search_and_      fx_index_search_and_reconstruct
+ *     reconstruct(x, k)    below)                     reconstruct
+ *   index.compute_        (re-scoring a candidate    faiss_IndexFlat_compute_     fx_index_compute_distance_subset
+ *     distance_subset      set from elsewhere)        distance_subset
  *   (is it an IDMap?)     --                         faiss_IndexIDMap_cast        fx_index_has_ids
  *   index.ntotal          faiss_store.py:53          faiss_Index_ntotal           fx_index_ntotal
  *   (re)IndexFlatL2(d)    faiss_store.py:126         faiss_Index_reset            fx_index_reset
@@ -372,6 +378,64 @@ int fx_index_reset(FxIndex* index);
 
 /* Copy rows [i0, i0+n) back as fp32 (host).  Used by write_index. */
 int fx_index_reconstruct_n(FxIndex* index, int64_t i0, int64_t n, float* out);
+
+/* ---- stored vectors by key: faiss reconstruct_batch / search_and_reconstruct /
+ * ---- compute_distance_subset ---------------------------------------------
+ *
+ *   faiss (Python)                                  faiss C API                              this ABI
+ *   index.reconstruct(key) / reconstruct_batch(keys) faiss_Index_reconstruct_batch           fx_index_reconstruct_batch
+ *   index.search_and_reconstruct(x, k)              faiss_Index_search_and_reconstruct       fx_index_search_and_reconstruct
+ *   index.compute_distance_subset(x, labels)        faiss_IndexFlat_compute_distance_subset  fx_index_compute_distance_subset
+ *
+ * Keys are the ids search returns: row + id_offset, or labels on a labelled
+ * index ("stable ids" above: the LAST row added with a label answers for it;
+ * one pass over the label array whatever n).  On the device every key is
+ * checked against the index's rows before an address is formed, and a key that
+ * names no row -- -1, the missing slot of a search result, included -- reads
+ * no memory:
+ *   - the NaN rule: its vector is a row of NaN, every bit set (fp32
+ *     0xFFFFFFFF, 16-bit 0xFFFF: faiss's memset(-1) of a missing result);
+ *   - the +-FLT_MAX rule: its distance is the missing slot's value, FLT_MAX
+ *     on an L2 index and -FLT_MAX on an IP index, so
+ *     compute_distance_subset(x, I) reproduces a padded search result.
+ * Vectors come back dense [n][d] as fp32 (the exact widening of bf16 / fp16
+ * rows) or in the index's storage dtype (the stored bytes). */
+
+/* out[i][0..d) = the stored vector of keys[i]; keys: n int64 on keys_mem, out
+ * on out_mem.  out_dtype: FX_F32 or the index's storage dtype (else
+ * FX_E_UNSUPPORTED).  HOST keys of an unlabelled index are validated first:
+ * any key outside [id_offset, id_offset + ntotal) is FX_E_ARG (faiss asserts
+ * key < ntotal), the message names the first bad key and nothing is written.
+ * DEVICE keys are read stream-ordered and cannot be validated without a sync:
+ * a bad key gives a NaN row.  On a labelled index an unknown label gives a NaN
+ * row in both modes (no sync in this layer).  With device keys and a device
+ * out the call is stream-ordered; a host out goes through a bounded stage
+ * buffer in chunks and blocks.  n == 0: FX_OK.  n > 2^31-1:
+ * FX_E_UNSUPPORTED. */
+int fx_index_reconstruct_batch(FxIndex* index, int64_t n, const int64_t* keys, int keys_mem,
+                               void* out, int out_dtype, int out_mem);
+/* fx_index_search (sel NULL; any k) or fx_index_search_sel (k <= FX_MAX_K,
+ * else FX_E_UNSUPPORTED) with the neighbours' vectors: D and I are exactly
+ * what those calls return, argument rules and error codes included, and
+ * R[i][j][0..d) (dtype r_dtype: FX_F32 or the storage dtype) is the stored
+ * vector of the ROW that ranked j for query i -- on a labelled index too, where
+ * I[i][j] is that row's label and labels may repeat.  Missing slots (I = -1)
+ * hold NaN.  With FX_MEM_DEVICE queries and results the whole call is
+ * stream-ordered: the gather is enqueued behind the device-decided re-scan and
+ * exact-fallback chain, no host sync.  Never recorded into or replayed from a
+ * search graph. */
+int fx_index_search_and_reconstruct(FxIndex* index, const FxSelector* sel, int64_t nq,
+                                    const void* q, int q_dtype, int q_mem, int k,
+                                    float* D, int64_t* I, void* R, int r_dtype, int out_mem);
+/* D[i][j] = the library's exact distance (fp64 sum over the stored row, one
+ * rounding to fp32; the arithmetic of the search's certified path, so the
+ * value search returns for that pair) of query i and the row keys[i][j]; k is
+ * the per-query candidate count, any positive value; keys [nq][k] int64 on
+ * keys_mem.  A key that names no row: +-FLT_MAX (above).  Stream-ordered when
+ * queries, keys and D are on the device.  nq == 0: FX_OK.  More than 2^31-1
+ * pairs per call: FX_E_UNSUPPORTED. */
+int fx_index_compute_distance_subset(FxIndex* index, int64_t nq, const void* q, int q_dtype, int q_mem,
+                                     int k, const int64_t* keys, int keys_mem, float* D, int out_mem);
 
 /* faiss.write_index / faiss.read_index on the IxF2 format (faiss_store.py:
  * 91,106): fourcc "IxF2", i32 d, i64 ntotal, i64 1<<20, i64 1<<20,

@@ -74,6 +74,9 @@ SIGNATURES = {
     "fx_index_last_dropped_candidates": (_i, [_vp, ctypes.POINTER(_i64)]),
     "fx_index_reset": (_i, [_vp]),
     "fx_index_reconstruct_n": (_i, [_vp, _i64, _i64, _vp]),
+    "fx_index_reconstruct_batch": (_i, [_vp, _i64, _vp, _i, _vp, _i, _i]),
+    "fx_index_search_and_reconstruct": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i]),
+    "fx_index_compute_distance_subset": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _i, _vp, _i]),
     "fx_index_write": (_i, [_vp, ctypes.c_char_p]),
     "fx_index_read": (_i, [ctypes.c_char_p, _i, _i, _pp]),
     "fx_merge_shards": (_i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -165,6 +165,18 @@ hipError_t carve(int64_t ntotal, int kdim, int qb, HkCarve* c) {
     return hipSuccess;
 }
 
+}  // namespace
+
+// k_hk_queries for a caller outside this file (fx_index_compute_distance_subset)
+hipError_t launch_f32_queries(const void* q, int q_dt, int64_t n, int d, int kdim, float* out, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (!q || !out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_hk_queries, dim3(grid_for(n * kdim)), dim3(HK_THREADS), 0, s, q, q_dt, n, d, kdim, out);
+    return hipGetLastError();
+}
+
+namespace {
+
 hipError_t launch_keys(const HugeKParams& p, const float* qf32, int qb, int idbits, uint64_t* keys, hipStream_t s) {
     const int64_t items = p.ntotal * ((qb + HK_QB - 1) / HK_QB);
     return dispatch_dt_metric<DT_STORED>(p.st_dt, p.metric, [&](auto dt, auto mt) {

@@ -1,5 +1,5 @@
 // fx_internal.h -- shared between the HIP translation units (fx_kernels.hip,
-// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip) and the host C ABI
+// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip) and the host C ABI
 // (fx_index.cpp): tiling constants, kernel parameter blocks, the launchers'
 // prototypes and their host-side helpers.  Not part of the public ABI
 // (include/fx_index.h).
@@ -399,6 +399,24 @@ hipError_t launch_rows_of_labels(const int64_t* labels, int64_t ntotal, const in
 // bit: removed), out of place (prefix: launch_keep_prefix's words)
 hipError_t launch_compact_labels(const int64_t* labels, const uint32_t* mask, const unsigned* prefix, int64_t ntotal,
                                  int64_t* dst, hipStream_t s);
+// stored vectors and exact distances by key (fx_recon.hip).  A key names local
+// row key - id_offset; one outside [id_offset, id_offset + ntotal) is checked
+// before any address is formed and reads no memory.
+// out[i][0..d) <- the stored row keys[i] (keys null: the implicit key key0 + i),
+// dense [n][d] of out_dt = F32 (exact widening) or st_dt (byte copy); a key
+// naming no row: a row of all-ones bits (NaN)
+hipError_t launch_gather_rows(const char* codes, int st_dt, int row_bytes, int64_t ntotal, const int64_t* keys,
+                              int64_t key0, int64_t id_offset, int64_t n, int d, void* out, int out_dt,
+                              hipStream_t s);
+// D[i][j] <- the refine's exact distance of query i (qf32: [nq][kdim] fp32, zero
+// padded) and row keys[i][j]; a key naming no row: FLT_MAX (L2) / -FLT_MAX (IP)
+hipError_t launch_subset_dist(int st_dt, int metric, const char* codes, int row_bytes, int kdim, int64_t ntotal,
+                              const float* qf32, int64_t nq, int k, const int64_t* keys, int64_t id_offset, float* D,
+                              hipStream_t s);
+// I[i] <- labels[I[i]] for rows 0 <= I[i] < ntotal, else -1
+hipError_t launch_label_ids(const int64_t* labels, int64_t ntotal, int64_t n, int64_t* I, hipStream_t s);
+// queries [n][d] (dtype q_dt, on the device) -> fp32 [n][kdim], zero padded (fx_hugek.hip: k_hk_queries)
+hipError_t launch_f32_queries(const void* q, int q_dt, int64_t n, int d, int kdim, float* out, hipStream_t s);
 // bits[0] <- max(bits[0], float bits of the largest of norms[0, n)) (atomicMax)
 hipError_t launch_norm_max(const float* norms, int64_t n, unsigned* bits, hipStream_t s);
 // fp32 code rows [r0, r1) -> their F32S scan image (same row stride)

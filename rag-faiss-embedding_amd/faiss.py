@@ -20,6 +20,11 @@ as faiss``:
   ``reconstruct(id)``: every row carries a caller-chosen int64 label that
   ``search`` / ``range_search`` return, selectors and ``remove_ids`` speak,
   and removals leave intact;
+* stored vectors by key, on the device: ``reconstruct(key)``,
+  ``reconstruct_batch(keys)``, ``search_and_reconstruct(x, k) -> (D, I, R)``
+  and ``compute_distance_subset(x, labels) -> D`` (keys are the ids ``search``
+  returns; one outside the index gives a NaN row / the missing slot's
+  distance from device keys and raises from host keys);
 * ``write_index(index, path)`` / ``read_index(path)`` on the IxF2 format
   (IxM2 for a labelled index).
 
@@ -553,6 +558,131 @@ class _FlatIndex:
                                                      out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    # -- stored vectors by key (include/fx_index.h "stored vectors by key") --------------
+    def _out_dtype(self, dtype, device_out: bool):
+        """(library dtype code, numpy / torch dtype) of a read-back: fp32
+        unless ``dtype="storage"`` asks for the stored bytes."""
+        if dtype not in (None, "float32", "storage"):
+            raise ValueError('dtype must be None, "float32" or "storage"')
+        name = self.storage_dtype if dtype == "storage" else "float32"
+        if device_out:
+            return _DTYPES[name], getattr(_torch(), name)
+        if name == "bfloat16":
+            raise TypeError("numpy has no bfloat16: read bfloat16 rows back with device keys (a tensor)")
+        return _DTYPES[name], np.dtype(name)
+
+    def reconstruct_batch(self, keys, dtype=None):
+        """``Index.reconstruct_batch``: the stored vectors of ``keys`` (ids as
+        ``search`` returns them: row + the id offset, or labels), shape
+        ``(n, d)``.  numpy (or any integer sequence) in -> numpy fp32 out, a
+        key outside the index raises; an int64 tensor on the index's GPU in ->
+        a device tensor out, stream-ordered, a key outside the index gives a
+        NaN row.  ``dtype="storage"``: the index's storage dtype (the stored
+        bytes) instead of fp32.  On a labelled index an unknown label gives a
+        NaN row either way."""
+        dev = _is_device_tensor(keys)
+        keys = _id_array(keys)
+        code, out_dt = self._out_dtype(dtype, dev)
+        if dev:
+            t = _torch()
+            assert keys.device.index == self.device, f"keys on cuda:{keys.device.index}, index on cuda:{self.device}"
+            out = t.empty((int(keys.numel()), self.d), dtype=out_dt, device=keys.device)
+            self._bind_stream(True)
+            self._check(self._lib.fx_index_reconstruct_batch(self._h, int(keys.numel()), ctypes.c_void_p(keys.data_ptr()),
+                                                             _lib.MEM_DEVICE, ctypes.c_void_p(out.data_ptr()), code,
+                                                             _lib.MEM_DEVICE))
+            return out
+        out = np.empty((int(keys.size), self.d), dtype=out_dt)
+        self._bind_stream(False)
+        self._check(self._lib.fx_index_reconstruct_batch(self._h, int(keys.size), ctypes.c_void_p(keys.ctypes.data),
+                                                         _lib.MEM_HOST, ctypes.c_void_p(out.ctypes.data), code,
+                                                         _lib.MEM_HOST))
+        return out
+
+    def reconstruct(self, key: int) -> np.ndarray:
+        """``Index.reconstruct``: the stored vector of one id, numpy fp32."""
+        return self.reconstruct_batch(np.array([int(key)], dtype=np.int64))[0]
+
+    def search_and_reconstruct(self, x, k: int, *, params=None, dtype=None) -> Tuple:
+        """``Index.search_and_reconstruct``: ``search(x, k)`` (or the filtered
+        search of ``params``) and the neighbours' stored vectors: ``(D, I, R)``
+        with ``R`` shaped ``(nq, k, d)``, ``R[i, j]`` the vector of the row that
+        ranked j (NaN where ``I == -1``).  numpy in -> numpy out; a device
+        tensor in -> device tensors out, the whole call stream-ordered.
+        ``dtype="storage"``: ``R`` in the index's storage dtype."""
+        k = int(k)
+        if k <= 0:
+            raise AssertionError("k must be positive")
+        sel = None if params is None else _selector_of(params)
+        dev = _is_device_tensor(x)
+        code, out_dt = self._out_dtype(dtype, dev)
+        if dev:
+            t = _torch()
+            assert x.dim() == 2 and x.shape[1] == self.d, "dimension mismatch"
+            assert x.device.index == self.device, f"queries on cuda:{x.device.index}, index on cuda:{self.device}"
+            x = x.contiguous()
+            nq = x.shape[0]
+            D = t.empty((nq, k), dtype=t.float32, device=x.device)
+            I = t.empty((nq, k), dtype=t.int64, device=x.device)
+            R = t.empty((nq, k, self.d), dtype=out_dt, device=x.device)
+            qptr, qdt, mem = ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x), _lib.MEM_DEVICE
+            ptrs = [ctypes.c_void_p(a.data_ptr()) for a in (D, I, R)]
+            self._bind_stream(True)
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+            assert x.ndim == 2 and x.shape[1] == self.d, "dimension mismatch"
+            nq = x.shape[0]
+            D = np.empty((nq, k), dtype=np.float32)
+            I = np.empty((nq, k), dtype=np.int64)
+            R = np.empty((nq, k, self.d), dtype=out_dt)
+            qptr, qdt, mem = ctypes.c_void_p(x.ctypes.data), _lib.F32, _lib.MEM_HOST
+            ptrs = [ctypes.c_void_p(a.ctypes.data) for a in (D, I, R)]
+            # (a selector built from a device tensor is read on the stream that tensor was made on)
+            self._bind_stream(sel is not None and _is_device_tensor(sel._spec()[1]))
+        self._check(self._lib.fx_index_search_and_reconstruct(self._h, sel._handle(self) if sel is not None else None,
+                                                              nq, qptr, qdt, mem, k, *ptrs, code, mem))
+        return D, I, R
+
+    def compute_distance_subset(self, x, labels):
+        """``IndexFlat.compute_distance_subset``: ``D[i, j]`` = the exact
+        distance of query row i and the stored vector of ``labels[i, j]`` (ids
+        as ``search`` returns them), ``labels`` shaped ``(nq, k)``.  An id
+        outside the index (-1 included) gives the missing slot's distance, so
+        ``compute_distance_subset(x, I)`` reproduces the ``D`` of ``search``.
+        numpy in -> numpy out; device tensors in -> a device tensor out
+        (stream-ordered)."""
+        dev = _is_device_tensor(x)
+        if dev:
+            t = _torch()
+            assert x.dim() == 2 and x.shape[1] == self.d, "dimension mismatch"
+            assert x.device.index == self.device, f"queries on cuda:{x.device.index}, index on cuda:{self.device}"
+            assert _is_device_tensor(labels) and labels.device == x.device and labels.dtype == t.int64, \
+                f"labels must be an int64 tensor on {x.device}"
+            assert labels.dim() == 2 and labels.shape[0] == x.shape[0], "labels must be shaped (nq, k)"
+            x, labels = x.contiguous(), labels.contiguous()
+            nq, k = labels.shape
+            D = t.empty((nq, k), dtype=t.float32, device=x.device)
+            if nq == 0 or k == 0:
+                return D
+            self._bind_stream(True)
+            self._check(self._lib.fx_index_compute_distance_subset(
+                self._h, nq, ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x), _lib.MEM_DEVICE, k,
+                ctypes.c_void_p(labels.data_ptr()), _lib.MEM_DEVICE, ctypes.c_void_p(D.data_ptr()), _lib.MEM_DEVICE))
+            return D
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        assert x.ndim == 2 and x.shape[1] == self.d, "dimension mismatch"
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        assert labels.ndim == 2 and labels.shape[0] == x.shape[0], "labels must be shaped (nq, k)"
+        nq, k = labels.shape
+        D = np.empty((nq, k), dtype=np.float32)
+        if nq == 0 or k == 0:
+            return D
+        self._bind_stream(False)
+        self._check(self._lib.fx_index_compute_distance_subset(
+            self._h, nq, ctypes.c_void_p(x.ctypes.data), _lib.F32, _lib.MEM_HOST, k, ctypes.c_void_p(labels.ctypes.data),
+            _lib.MEM_HOST, ctypes.c_void_p(D.ctypes.data), _lib.MEM_HOST))
+        return D
+
     def set_id_offset(self, offset: int) -> None:
         self._check(self._lib.fx_index_set_id_offset(self._h, int(offset)))
         self._id_offset = int(offset)  # (built selectors are keyed on it: ids are row + offset)
@@ -642,6 +772,17 @@ class IndexIDMap:
         ascending ROW within a query."""
         return self.index.range_search(x, radius, params=params)
 
+    def search_and_reconstruct(self, x, k: int, *, params=None, dtype=None) -> Tuple:
+        """``search_and_reconstruct`` of the wrapped index: ``I`` holds labels,
+        ``R[i, j]`` the vector of the ROW that ranked j (labels may repeat)."""
+        return self.index.search_and_reconstruct(x, k, params=params, dtype=dtype)
+
+    def compute_distance_subset(self, x, labels):
+        """``compute_distance_subset`` of the wrapped index with labels as keys
+        (of a repeated label: its last row; an unknown one: the missing slot's
+        distance)."""
+        return self.index.compute_distance_subset(x, labels)
+
     def remove_ids(self, x) -> int:
         """Remove every row whose label ``x`` selects (an ``IDSelector``, or
         labels as ``IDSelectorBatch`` takes them); returns the rows removed."""
@@ -660,12 +801,26 @@ class IndexIDMap:
 
 
 class IndexIDMap2(IndexIDMap):
-    """``faiss.IndexIDMap2``: ``IndexIDMap`` plus ``reconstruct(id)``."""
+    """``faiss.IndexIDMap2``: ``IndexIDMap`` plus ``reconstruct(id)`` and
+    ``reconstruct_batch(ids)``."""
+
+    def reconstruct_batch(self, labels, dtype=None):
+        """The stored vectors of ``labels`` (of a repeated label: the last row
+        added with it), numpy in -> numpy out, device tensor in -> device tensor
+        out; an unknown label gives a NaN row (no synchronisation to find out)."""
+        return self.index.reconstruct_batch(labels, dtype=dtype)
 
     def reconstruct(self, key: int) -> np.ndarray:
         """The stored vector of label ``key`` (of the last row added with it,
         as ``IndexIDMap2.rev_map`` keeps); an unknown label raises
         ``RuntimeError``."""
+        batch = getattr(self.index, "reconstruct_batch", None)
+        if batch is not None:  # one call: label -> row and the gather both on the device
+            v = np.asarray(batch(np.array([int(key)], dtype=np.int64)))[0]
+            if np.isnan(v).all():  # the library's answer for a label no row carries
+                raise RuntimeError(f"reconstruct: key {int(key)} not found")
+            return v
+        # (a wrapped flat-index look-alike without the batch read-back: its row, then the row's vector)
         row = int(self.index.rows_of_ids(np.array([int(key)], dtype=np.int64))[0])
         if row < 0:
             raise RuntimeError(f"reconstruct: key {int(key)} not found")

@@ -89,21 +89,81 @@ def selector_for_documents(doc_ids: Sequence[int], allowed_ids: Iterable[int]):
     return fx.SearchParameters(sel=fx.IDSelectorBatch(rows.astype(np.int64)))
 
 
+def mmr_pick(sim_q: np.ndarray, vectors: np.ndarray, k: int, lam: float, l2: bool) -> List[int]:
+    """Greedy maximal-marginal-relevance pick of ``k`` of n ranked candidates:
+    repeatedly the candidate c with the largest
+
+        lam * s(q, c) - (1 - lam) * max over picked p of s(c, p)
+
+    where ``sim_q[c]`` = s(q, c) and s between candidates is ``-|c - p|^2``
+    (``l2``) or the dot product, from ``vectors`` (n, d) in float64.  The first
+    pick is rank 0; ties go to the earlier rank.  Returns the picked ranks in
+    pick order."""
+    n = len(sim_q)
+    if n == 0 or k <= 0:
+        return []
+    sim_q = np.asarray(sim_q, dtype=np.float64)
+    v = np.asarray(vectors, dtype=np.float64)
+
+    def sim_to(p: int) -> np.ndarray:
+        return -((v - v[p]) ** 2).sum(axis=1) if l2 else v @ v[p]
+
+    picked = [0]
+    closest = sim_to(0)  # every candidate's largest similarity to a picked one
+    while len(picked) < min(int(k), n):
+        value = lam * sim_q - (1.0 - lam) * closest
+        value[picked] = -np.inf
+        j = int(np.argmax(value))  # (the first maximum: the earlier rank)
+        picked.append(j)
+        closest = np.maximum(closest, sim_to(j))
+    return picked
+
+
+def _diverse_search(index, query_embeddings, k: int, params, diversity: float, fetch_k: Optional[int]):
+    """``search`` re-ranked for diversity: ``fetch_k`` candidates (default 4k)
+    and their stored vectors from one ``search_and_reconstruct``, then
+    ``mmr_pick`` per query.  Returns (D, I) shaped (nq, k), missing slots -1."""
+    lam = float(diversity)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"diversity must be in [0, 1] (got {diversity})")
+    fetch = max(int(k), int(fetch_k) if fetch_k is not None else 4 * int(k))
+    Dc, Ic, Rc = index.search_and_reconstruct(query_embeddings, fetch, params=params)
+    Dc, Ic, Rc = _to_numpy(Dc), _to_numpy(Ic), _to_numpy(Rc)
+    l2 = getattr(index, "metric_type", 1) == 1
+    D = np.full((Ic.shape[0], int(k)), np.finfo(np.float32).max if l2 else -np.finfo(np.float32).max, dtype=np.float32)
+    I = np.full((Ic.shape[0], int(k)), -1, dtype=np.int64)
+    for qi in range(Ic.shape[0]):
+        live = np.flatnonzero(Ic[qi] >= 0)  # (ranked first: missing slots pad the end)
+        sim_q = -Dc[qi, live].astype(np.float64) if l2 else Dc[qi, live].astype(np.float64)
+        picks = live[mmr_pick(sim_q, Rc[qi, live], int(k), lam, l2)]
+        D[qi, :len(picks)] = Dc[qi, picks]
+        I[qi, :len(picks)] = Ic[qi, picks]
+    return D, I
+
+
 def search_similar_documents(index, doc_ids: Sequence[int], store: DocumentStore, query_embeddings,
-                             k: int = 5, allowed_ids: Optional[Iterable[int]] = None) -> List[List[Dict]]:
+                             k: int = 5, allowed_ids: Optional[Iterable[int]] = None,
+                             diversity: Optional[float] = None, fetch_k: Optional[int] = None) -> List[List[Dict]]:
     """Batched ``RAGDatabaseManager.search_similar_documents``
     (rag_datastore_manager.py:211-238): for every query row, the documents
     of its k nearest index rows, nearest first, each with ``distance`` (the
     squared L2 distance the index returned).  ``doc_ids`` is the row -> doc
     id mapping (faiss_index.bin.mapping).  ``allowed_ids`` (document ids):
-    only those documents are ranked, by the index's filtered search.  Errors
-    are logged and give empty lists, as the reference's blanket ``except``
-    does."""
+    only those documents are ranked, by the index's filtered search.
+    ``diversity`` (lambda in [0, 1]; None: off): the k results are picked
+    greedily by maximal marginal relevance (``mmr_pick``) among the
+    ``fetch_k`` (default 4k) nearest rows, whose vectors come from the
+    index's ``search_and_reconstruct``; 1 is the plain ranking, smaller
+    values trade nearness for spread.  Errors are logged and give empty
+    lists, as the reference's blanket ``except`` does."""
     try:
-        if allowed_ids is None:
+        params = None if allowed_ids is None else selector_for_documents(doc_ids, allowed_ids)
+        if diversity is not None:
+            D, I = _diverse_search(index, query_embeddings, int(k), params, diversity, fetch_k)
+        elif allowed_ids is None:
             D, I = index.search(query_embeddings, int(k))
         else:
-            D, I = index.search(query_embeddings, int(k), params=selector_for_documents(doc_ids, allowed_ids))
+            D, I = index.search(query_embeddings, int(k), params=params)
         D, I = _to_numpy(D), _to_numpy(I)
         ids = np.asarray(doc_ids, dtype=np.int64)
         valid = (I >= 0) & (I < len(ids))
@@ -229,12 +289,18 @@ class RetrievalEngine:
             return self.vectorizer.generate_embeddings_device(texts)
         return np.asarray(self.vectorizer.generate_embeddings(texts), dtype=np.float32)
 
-    def search(self, texts: List[str], k: int = 5, allowed_ids: Optional[Iterable[int]] = None) -> List[List[Dict]]:
-        """``allowed_ids``: rank only these document ids (filtered search)."""
+    def search(self, texts: List[str], k: int = 5, allowed_ids: Optional[Iterable[int]] = None,
+               diversity: Optional[float] = None, fetch_k: Optional[int] = None) -> List[List[Dict]]:
+        """``allowed_ids``: rank only these document ids (filtered search).
+        ``diversity`` / ``fetch_k``: maximal-marginal-relevance re-ranking
+        (``search_similar_documents``)."""
         if not texts:
             return []
+        if diversity is None:
+            return search_similar_documents(self.index, self.doc_ids, self.store, self.embed(texts), k,
+                                            allowed_ids=allowed_ids)
         return search_similar_documents(self.index, self.doc_ids, self.store, self.embed(texts), k,
-                                        allowed_ids=allowed_ids)
+                                        allowed_ids=allowed_ids, diversity=diversity, fetch_k=fetch_k)
 
     def search_within(self, texts: List[str], *, max_distance: Optional[float] = None,
                       min_score: Optional[float] = None) -> List[List[Dict]]:

@@ -42,6 +42,11 @@ class ShardedIndexFlatL2:
     ``remove_ids`` is not offered either (as there is no ``reset``): a removal
     renumbers a shard's rows densely, so the ranks would have to agree on new
     shard offsets and ``n_total`` before the next search.
+
+    ``reconstruct_batch`` / ``search_and_reconstruct`` /
+    ``compute_distance_subset`` are not offered either: after the merge a
+    neighbour's vector lives on another rank, so each would need an exchange
+    of vectors by owner on top of the (nq x k) all_gather.
     """
 
     def __init__(self, d: int, n_total: int, dtype: str = "float32", group=None, device: Optional[int] = None,
