@@ -140,7 +140,10 @@ int fx_index_set_stream(FxIndex* index, void* stream);
  * the option drops a grown buffer), "remove_stage" 0 (= 256 MiB) or row
  * bytes .. 2^32 (bytes of the staging buffer fx_index_remove_ids gathers
  * overlapping chunks of rows into; a smaller one means more, smaller
- * chunks).  None changes results, only
+ * chunks), "kmeans_chunk" 0 (= 131,072) or 1 .. 2^30 (rows per chunk of
+ * fx_kmeans_step / fx_kmeans_update; the chunk order is part of a k-means
+ * result's summation order, so this one may change the last bits of the
+ * centroids).  None of the others changes results, only
  * speed.  Unknown name or out-of-range value: FX_E_ARG.  (The diagnostic
  * build libfx_index_diag.so adds test hooks -- "force_fallback",
  * "scan_dbg" -- that the product library does not have.) */
@@ -436,6 +439,81 @@ int fx_index_search_and_reconstruct(FxIndex* index, const FxSelector* sel, int64
  * pairs per call: FX_E_UNSUPPORTED. */
 int fx_index_compute_distance_subset(FxIndex* index, int64_t nq, const void* q, int q_dtype, int q_mem,
                                      int k, const int64_t* keys, int keys_mem, float* D, int out_mem);
+
+/* ---- k-means: faiss Kmeans / Clustering ------------------------------------
+ *
+ *   faiss (Python)                      faiss C++ / C API                               this ABI
+ *   faiss.Kmeans(d, k).train(x)         Clustering::train / faiss_Clustering_train      fx_kmeans_step + fx_kmeans_finish, per iteration
+ *   kmeans.index.search(x, 1)           Index::assign / faiss_Index_assign              fx_index_search (k = 1) on the centroid index
+ *
+ * One iteration of Lloyd's algorithm over a centroid index (an unlabelled flat
+ * index with id offset 0 whose k = ntotal rows are the centroids).  The
+ * assignment is the index's own k = 1 search, so its ids are bit-exact; the
+ * update is bitwise reproducible: member lists from a stable radix sort of
+ * (cluster << 32 | row) keys, fp64 sums in a fixed order, no floating-point
+ * atomics.  Two runs of the same calls give the same bits; the result depends
+ * on the rows, the assignment and the chunking only.
+ *
+ * Buffers: sums [k][d] fp64, counts [k] int64, obj one fp64, assign [n] int64,
+ * dist [n] fp32, centroids_out [k][d] fp32 and n_split one int64 are always
+ * DEVICE memory; x is on x_mem.  With FX_MEM_DEVICE x every call here is
+ * stream-ordered on the index's stream (workspace growth may synchronise
+ * through hipMalloc / hipFree); host x is staged through a bounded pinned
+ * buffer (64 MiB) chunk by chunk and the call blocks.  Large n is cut into
+ * chunks of the option "kmeans_chunk" rows (default 131,072: the search
+ * workspace of a chunk stays near 1 GiB at d = 768 whatever n is), and the
+ * chunks' results are accumulated in chunk order.
+ *
+ * An assign[i] outside [0, k) -- a padded search's -1 included -- forms no
+ * key and no address: the row is skipped and counted.  A host-x call returns
+ * FX_E_INTEGRITY when it skipped one; after device-x calls fx_kmeans_status
+ * reports the count.
+ *
+ * Errors of the three calls: FX_E_ARG for a null index, an empty centroid
+ * index, n < 0, a dtype outside the three, a bad x_mem, or null sums /
+ * counts / obj (fx_kmeans_finish: any null buffer); FX_E_UNSUPPORTED for a
+ * labelled centroid index, a non-zero id offset, or k > 2^31-1.  n == 0 is
+ * FX_OK and changes nothing.  Never recorded into a search graph. */
+
+/* assign / dist <- the k = 1 search of x[n][d] over the centroids (NULL: kept
+ * in the library's workspace), then sums[c] = the fp64 sum of the rows
+ * assigned to c, counts[c] = their number, obj = the fp64 sum of their
+ * distances (L2 index: squared distances; IP index: inner products).
+ * accumulate != 0 adds to what sums / counts / obj hold (a training set passed
+ * in several calls); 0 overwrites them. */
+int fx_kmeans_step(FxIndex* centroids, int64_t n, const void* x, int x_dtype, int x_mem,
+                   int64_t* assign, float* dist,      /* device, n each; NULL = library workspace   */
+                   double* sums, int64_t* counts,     /* device, [k][d] and [k]                     */
+                   double* obj,                       /* device, one fp64                           */
+                   int accumulate);
+/* The update half alone, from the caller's assignment (device, n int64;
+ * dist: device, n fp32, or NULL: obj gets 0 added).  What fx_kmeans_step runs
+ * after its search. */
+int fx_kmeans_update(FxIndex* centroids, int64_t n, const void* x, int x_dtype, int x_mem,
+                     const int64_t* assign, const float* dist, double* sums, int64_t* counts,
+                     double* obj, int accumulate);
+/* centroids_out[c] = (float)(sums[c] / counts[c]) where counts[c] > 0; an
+ * empty cluster keeps the row the index stores and is then repaired as
+ * faiss's split_clusters does, except for the donor: faiss draws it at random
+ * in proportion to the cluster sizes, here it is the cluster with the largest
+ * working count (ties: the smaller index), so a training is reproducible.
+ * For each empty ci in ascending order, with donor cj: c[ci] = c[cj]; for
+ * even j c[ci][j] *= 1 + EPS and c[cj][j] *= 1 - EPS, for odd j the signs
+ * swapped (EPS = 1/1024, fp32); working counts h[ci] = h[cj] / 2, h[cj] -=
+ * h[ci].  *n_split = the repairs.  spherical != 0 then divides every centroid
+ * by its L2 norm (an fp64 sum; each element rounded once).  Last, the index
+ * is reset and the k new centroids are added to it, stream-ordered, so the
+ * next fx_kmeans_step / search sees them (selectors built before are stale). */
+int fx_kmeans_finish(FxIndex* centroids, const double* sums, const int64_t* counts, int spherical,
+                     float* centroids_out /* device [k][d] */, int64_t* n_split /* device */);
+/* Waits for the index's stream; *bad_assign = the assignments outside [0, k)
+ * skipped since the last read (then 0 again).  FX_E_INTEGRITY when non-zero. */
+int fx_kmeans_status(FxIndex* centroids, int64_t* bad_assign);
+/* With fx_index_profile on, the k-means calls record events around their
+ * parts; this waits and returns the milliseconds since the last read: the
+ * searches, key build + sort + segments, sum + fold, and the finishes. */
+int fx_kmeans_profile_read(FxIndex* centroids, double* assign_ms, double* sort_ms, double* sum_ms,
+                           double* finish_ms);
 
 /* faiss.write_index / faiss.read_index on the IxF2 format (faiss_store.py:
  * 91,106): fourcc "IxF2", i32 d, i64 ntotal, i64 1<<20, i64 1<<20,

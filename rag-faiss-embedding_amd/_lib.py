@@ -77,6 +77,11 @@ SIGNATURES = {
     "fx_index_reconstruct_batch": (_i, [_vp, _i64, _vp, _i, _vp, _i, _i]),
     "fx_index_search_and_reconstruct": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i]),
     "fx_index_compute_distance_subset": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _i, _vp, _i]),
+    "fx_kmeans_step": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "fx_kmeans_update": (_i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "fx_kmeans_finish": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "fx_kmeans_status": (_i, [_vp, ctypes.POINTER(_i64)]),
+    "fx_kmeans_profile_read": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 4),
     "fx_index_write": (_i, [_vp, ctypes.c_char_p]),
     "fx_index_read": (_i, [ctypes.c_char_p, _i, _i, _pp]),
     "fx_merge_shards": (_i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -87,6 +87,13 @@ constexpr int RANGE_CAP_DEFAULT = 1 << 20, RANGE_CAP_MAX = 1 << 30;
 // otherwise (one row .. REMOVE_STAGE_MAX)
 constexpr int64_t REMOVE_STAGE_DEFAULT = 256ll << 20, REMOVE_STAGE_MAX = 1ll << 32;
 
+// rows per chunk of fx_kmeans_step unless the option kmeans_chunk says
+// otherwise: the k = 1 search of a chunk keeps ~ (8 + 2 row_bytes) B of
+// workspace per row plus its candidate lists, so 131,072 rows of d = 768 stay
+// near 1 GiB whatever n is; the option's limit keeps a chunk's member blocks
+// (<= rows / KM_M + rows) below 2^31
+constexpr int KMEANS_CHUNK_DEFAULT = 1 << 17, KMEANS_CHUNK_MAX = 1 << 30;
+
 // Per-index tuning options.  Initial values come from the FX_* environment
 // variables, read ONCE when the index is created (never on the search path);
 // fx_index_set_option changes them afterwards (range-checked: opt_range).
@@ -133,6 +140,8 @@ struct Options {
                              // default RANGE_CAP_DEFAULT; a call that finds more grows it and scans again)
     int64_t remove_stage = 0;  // FX_REMOVE_STAGE: bytes of remove_ids' staging buffer (0: REMOVE_STAGE_DEFAULT;
                                // row_bytes .. REMOVE_STAGE_MAX, checked by fx_index_set_option / at use)
+    int kmeans_chunk = 0;    // FX_KMEANS_CHUNK: rows per chunk of fx_kmeans_step / fx_kmeans_update (0: the
+                             // default KMEANS_CHUNK_DEFAULT; 1 .. 2^30)
     int host_spin = 1;       // FX_HOST_SPIN: a host-output search waits for its results by polling the
                              // stream (1) instead of a blocking hipStreamSynchronize (0)
 #ifdef FX_DIAG
@@ -172,6 +181,8 @@ struct Options {
         num("FX_REFINE_WAVES", refine_waves);
         num("FX_RANGE_CAP", range_cap);
         if (range_cap < 0 || range_cap > RANGE_CAP_MAX) range_cap = 0;
+        num("FX_KMEANS_CHUNK", kmeans_chunk);
+        if (kmeans_chunk < 0 || kmeans_chunk > KMEANS_CHUNK_MAX) kmeans_chunk = 0;
         if (const char* e = getenv("FX_REMOVE_STAGE"); e && *e) remove_stage = atoll(e);
         if (remove_stage < 0 || remove_stage > REMOVE_STAGE_MAX) remove_stage = 0;
         if (refine_waves != 4 && refine_waves != 8 && refine_waves != 16) refine_waves = REFINE_WG_WAVES;
@@ -218,6 +229,7 @@ struct Options {
             {"convoy_every", &convoy_every, 1, 8, nullptr, 0},
             {"refine_waves", &refine_waves, 4, 16, kWaves, 3},
             {"range_cap", &range_cap, 0, RANGE_CAP_MAX, nullptr, 0},
+            {"kmeans_chunk", &kmeans_chunk, 0, KMEANS_CHUNK_MAX, nullptr, 0},
 #ifdef FX_DIAG
             {"force_fallback", &force_fallback, 0, 2, nullptr, 0},
             {"scan_dbg", &scan_dbg, 0, 1 << 20, nullptr, 0},
@@ -366,6 +378,15 @@ struct FxIndex {
     // keys and queries, a labelled index's keys as rows, the fp32 queries, device results of a host
     // output -- none of them a buffer a search graph captured
     DevBuf rc_in, rc_rows, rc_qf32, rc_out;
+    // k-means (fx_kmeans.hip): the update's workspace, the assignment / distances of a chunk when the
+    // caller keeps none, staged host rows (device and pinned), the repair's working counts, and the
+    // device counter of assignments outside [0, k) with its pinned mirror
+    DevBuf km_ws, km_out, km_x, km_h;
+    char* km_pin = nullptr;
+    size_t km_pin_bytes = 0;
+    unsigned long long* km_bad = nullptr;
+    unsigned long long* km_bad_pin = nullptr;
+    std::vector<hipEvent_t> km_ev, km_ev_fin;  // profiling: 4 events per chunk of a step, 2 per finish
     DevBuf conv;  // k_scan_v5 convoy words (CONV_WORDS; zeroed once, then only hints)
     int last_plan[3] = {0, 0, 0};  // the last search's scan plan: tile rows (128 k_scan_v4, 64 k_scan_v5), qt, splits
     // profiling
@@ -1626,7 +1647,8 @@ void fx_index_free(FxIndex* h) {
                           &h->rq_cand_d, &h->rq_cand_i, &h->rq_flag, &h->hk_ws, &h->hout, &h->conv, &h->rg_qin,
                           &h->rg_qf32, &h->rg_qop, &h->rg_eps, &h->rg_rho, &h->rg_shift, &h->rg_thr, &h->rg_cnt,
                           &h->rg_cand, &h->rg_dist, &h->rg_sorted, &h->rg_temp, &h->rg_lims, &h->rg_D, &h->rg_I,
-                          &h->rm_ws, &h->rc_in, &h->rc_rows, &h->rc_qf32, &h->rc_out})
+                          &h->rm_ws, &h->rc_in, &h->rc_rows, &h->rc_qf32, &h->rc_out, &h->km_ws, &h->km_out, &h->km_x,
+                          &h->km_h})
             b->release();
         graph_release(h);
         if (h->ghq) (void)hipHostFree(h->ghq);
@@ -1634,6 +1656,11 @@ void fx_index_free(FxIndex* h) {
         if (h->hpin) (void)hipHostFree(h->hpin);
         if (h->qpin) (void)hipHostFree(h->qpin);
         if (h->pin_nf) (void)hipHostFree(h->pin_nf);
+        if (h->km_pin) (void)hipHostFree(h->km_pin);
+        if (h->km_bad) (void)hipFree(h->km_bad);
+        if (h->km_bad_pin) (void)hipHostFree(h->km_bad_pin);
+        for (hipEvent_t e : h->km_ev) (void)hipEventDestroy(e);
+        for (hipEvent_t e : h->km_ev_fin) (void)hipEventDestroy(e);
         for (auto& pr : h->ev_scan) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
         for (auto& pr : h->ev_merge) (void)hipEventDestroy(pr.second);
         if (h->switch_ev) (void)hipEventDestroy(h->switch_ev);
@@ -2574,6 +2601,233 @@ int fx_index_compute_distance_subset(FxIndex* h, int64_t nq, const void* q, int 
                                (const float*)h->rc_qf32.p, nq, k, dkeys, id_offset, Dd, s));
     if (out_mem == FX_MEM_HOST) HIP_TRY(hipMemcpyAsync(D, Dd, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     if (out_mem == FX_MEM_HOST || stage_q || stage_k) HIP_TRY(hipStreamSynchronize(s));
+    return FX_OK;
+}
+
+// ---- k-means (fx_kmeans.hip) -------------------------------------------------
+
+namespace {
+
+// pinned staging of host training rows, per chunk
+constexpr int64_t KMEANS_PIN_BYTES = 64ll << 20;
+
+int km_check_index(const FxIndex* h, const char* who) {
+    if (h->ntotal <= 0) return set_err(FX_E_ARG, "%s: the centroid index is empty", who);
+    if (h->has_ids) return set_err(FX_E_UNSUPPORTED, "%s: the centroid index carries labels (add_with_ids)", who);
+    if (h->id_offset != 0)
+        return set_err(FX_E_UNSUPPORTED, "%s: the centroid index has id offset %lld", who, (long long)h->id_offset);
+    if (h->ntotal > (int64_t)INT32_MAX) return set_err(FX_E_UNSUPPORTED, "%s: more than 2^31-1 centroids", who);
+    return FX_OK;
+}
+
+hipError_t km_ensure_bad(FxIndex* h) {
+    if (h->km_bad) return hipSuccess;
+    hipError_t e = hipMalloc((void**)&h->km_bad, 8);
+    if (e == hipSuccess) e = hipMemset(h->km_bad, 0, 8);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->km_bad_pin, 8, hipHostMallocDefault);
+    return e;
+}
+
+// the skipped-assignment count since the last read (waits for the stream), then 0 again
+int km_read_bad(FxIndex* h, int64_t* out) {
+    *out = 0;
+    if (!h->km_bad) return FX_OK;
+    hipStream_t s = h->stream();
+    HIP_TRY(hipMemcpyAsync(h->km_bad_pin, h->km_bad, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(h->km_bad, 0, 8, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = (int64_t)*h->km_bad_pin;
+    return FX_OK;
+}
+
+int km_bad_error(int64_t bad, int64_t k) {
+    return set_err(FX_E_INTEGRITY, "kmeans: %lld assignments outside [0, %lld) were skipped", (long long)bad,
+                   (long long)k);
+}
+
+// fx_kmeans_step (search) / fx_kmeans_update: the rows in chunks, each chunk's
+// assignment (searched, or the caller's) and its update, accumulated in chunk order
+int km_run(FxIndex* h, int64_t n, const void* x, int x_dtype, int x_mem, int64_t* assign, float* dist, bool search,
+           double* sums, int64_t* counts, double* obj, int accumulate) {
+    hipStream_t s = h->stream();
+    const int64_t k = h->ntotal;
+    const int64_t rowb = (int64_t)h->d * dtype_size(x_dtype);
+    const bool host = x_mem == FX_MEM_HOST;
+    int64_t chunk = h->opt.kmeans_chunk > 0 ? h->opt.kmeans_chunk : (int)KMEANS_CHUNK_DEFAULT;
+    if (host) chunk = std::min(chunk, std::max<int64_t>(1, KMEANS_PIN_BYTES / rowb));
+    chunk = std::min(chunk, n);
+    HIP_TRY(km_ensure_bad(h));
+    if (search && (!assign || !dist)) HIP_TRY(h->km_out.ensure((size_t)chunk * 12));
+    if (host) {
+        HIP_TRY(h->km_x.ensure((size_t)(chunk * rowb)));
+        HIP_TRY(ensure_pinned(h->km_pin, h->km_pin_bytes, (size_t)(chunk * rowb)));
+    }
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int64_t nr = std::min(chunk, n - r0);
+        size_t ws_bytes = 0;  // (per chunk: the sort's temporaries need not grow with the rows)
+        HIP_TRY(km_workspace(nr, k, h->d, &ws_bytes));
+        HIP_TRY(h->km_ws.ensure(ws_bytes));
+        const void* xd = (const char*)x + r0 * rowb;
+        if (host) {
+            memcpy(h->km_pin, xd, (size_t)(nr * rowb));
+            HIP_TRY(hipMemcpyAsync(h->km_x.p, h->km_pin, (size_t)(nr * rowb), hipMemcpyHostToDevice, s));
+            xd = h->km_x.p;
+        }
+        int64_t* a = assign ? assign + r0 : (int64_t*)h->km_out.p;
+        float* dd = dist ? dist + r0 : (search ? (float*)((char*)h->km_out.p + (size_t)chunk * 8) : nullptr);
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        if (h->profile) {
+            for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+            h->km_ev.insert(h->km_ev.end(), ev, ev + 4);
+            HIP_TRY(hipEventRecord(ev[0], s));
+        }
+        if (search) {
+            // the index's own device-output k = 1 search: every plan, the re-scan and the exact fallback
+            const int rc = do_search(h, nr, xd, x_dtype, FX_MEM_DEVICE, 1, dd, a, FX_MEM_DEVICE);
+            if (rc != FX_OK) return rc;
+        }
+        if (h->profile) HIP_TRY(hipEventRecord(ev[1], s));
+        KmUpdate u{};
+        u.x = xd;
+        u.x_dt = x_dtype;
+        u.n = nr;
+        u.d = h->d;
+        u.k = k;
+        u.assign = a;
+        u.dist = dd;
+        u.sums = sums;
+        u.counts = counts;
+        u.obj = obj;
+        u.accumulate = accumulate != 0 || r0 > 0;
+        u.bad = h->km_bad;
+        HIP_TRY(launch_km_update(u, h->km_ws.p, h->km_ws.bytes, s, ev[2]));
+        if (h->profile) HIP_TRY(hipEventRecord(ev[3], s));
+        if (host) HIP_TRY(hipStreamSynchronize(s));  // (the staging buffers are free again)
+    }
+    if (!host) return FX_OK;
+    // a host call has waited for its work: its skipped entries are known now
+    int64_t bad = 0;
+    if (const int rc = km_read_bad(h, &bad); rc != FX_OK) return rc;
+    return bad > 0 ? km_bad_error(bad, k) : FX_OK;
+}
+
+int km_check_args(const FxIndex* h, int64_t n, int x_dtype, int x_mem, const double* sums, const int64_t* counts,
+                  const double* obj) {
+    // (the index last: the other checks are then reachable without a device)
+    if (n < 0) return set_err(FX_E_ARG, "negative n");
+    if (!check_dtype(x_dtype)) return set_err(FX_E_ARG, "bad x dtype %d", x_dtype);
+    if (x_mem != FX_MEM_HOST && x_mem != FX_MEM_DEVICE) return set_err(FX_E_ARG, "bad x_mem %d", x_mem);
+    if (!sums || !counts || !obj) return set_err(FX_E_ARG, "null sums / counts / obj");
+    if (!h) return set_err(FX_E_ARG, "null index");
+    return FX_OK;
+}
+
+}  // namespace
+
+int fx_kmeans_step(FxIndex* h, int64_t n, const void* x, int x_dtype, int x_mem, int64_t* assign, float* dist,
+                   double* sums, int64_t* counts, double* obj, int accumulate) {
+    if (const int rc = km_check_args(h, n, x_dtype, x_mem, sums, counts, obj); rc != FX_OK) return rc;
+    if (n == 0) return FX_OK;
+    if (!x) return set_err(FX_E_ARG, "null x");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (const int rc = km_check_index(h, "kmeans_step"); rc != FX_OK) return rc;
+    DeviceGuard g(h->device);
+    if (!g.ok) return set_err(FX_E_HIP, "hipSetDevice(%d) failed", h->device);
+    return km_run(h, n, x, x_dtype, x_mem, assign, dist, true, sums, counts, obj, accumulate);
+}
+
+int fx_kmeans_update(FxIndex* h, int64_t n, const void* x, int x_dtype, int x_mem, const int64_t* assign,
+                     const float* dist, double* sums, int64_t* counts, double* obj, int accumulate) {
+    if (const int rc = km_check_args(h, n, x_dtype, x_mem, sums, counts, obj); rc != FX_OK) return rc;
+    if (n == 0) return FX_OK;
+    if (!x || !assign) return set_err(FX_E_ARG, "null x / assign");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (const int rc = km_check_index(h, "kmeans_update"); rc != FX_OK) return rc;
+    DeviceGuard g(h->device);
+    if (!g.ok) return set_err(FX_E_HIP, "hipSetDevice(%d) failed", h->device);
+    return km_run(h, n, x, x_dtype, x_mem, const_cast<int64_t*>(assign), const_cast<float*>(dist), false, sums, counts,
+                  obj, accumulate);
+}
+
+int fx_kmeans_finish(FxIndex* h, const double* sums, const int64_t* counts, int spherical, float* centroids_out,
+                     int64_t* n_split) {
+    if (!sums || !counts || !centroids_out || !n_split) return set_err(FX_E_ARG, "null buffer");
+    if (!h) return set_err(FX_E_ARG, "null index");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (const int rc = km_check_index(h, "kmeans_finish"); rc != FX_OK) return rc;
+    DeviceGuard g(h->device);
+    if (!g.ok) return set_err(FX_E_HIP, "hipSetDevice(%d) failed", h->device);
+    hipStream_t s = h->stream();
+    const int64_t k = h->ntotal;
+    HIP_TRY(h->km_h.ensure((size_t)k * 8));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (h->profile) {
+        for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+        h->km_ev_fin.insert(h->km_ev_fin.end(), ev, ev + 2);
+        HIP_TRY(hipEventRecord(ev[0], s));
+    }
+    KmFinish f{};
+    f.sums = sums;
+    f.counts = counts;
+    f.k = k;
+    f.d = h->d;
+    f.codes = h->codes;
+    f.st_dt = h->dtype;
+    f.row_bytes = h->row_bytes;
+    f.spherical = spherical;
+    f.cent = centroids_out;
+    f.h = (int64_t*)h->km_h.p;
+    f.n_split = n_split;
+    HIP_TRY(launch_km_finish(f, s));
+    // fx_index_reset and a device-side fx_index_add of the k new rows, both
+    // stream-ordered: the rows [0, k) are rewritten in place (nothing grows, the
+    // rows past k keep their zero codes and +inf norms), the scan image and
+    // its centre are rebuilt by the next search, selectors from before are stale
+    HIP_TRY(hipMemsetAsync(h->max_sq_bits, 0, 8, s));
+    h->ntotal = 0;
+    ++h->epoch;
+    h->img_rows = 0;
+    h->mu_rows = 0;
+    h->rg_nq = -1;
+    h->rg_total = 0;
+    if (const int rc = append_rows(h, k, centroids_out, FX_F32, FX_MEM_DEVICE); rc != FX_OK) return rc;
+    h->ntotal = k;
+    if (h->profile) HIP_TRY(hipEventRecord(ev[1], s));
+    return FX_OK;
+}
+
+int fx_kmeans_status(FxIndex* h, int64_t* bad_assign) {
+    if (!h || !bad_assign) return set_err(FX_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    if (const int rc = km_read_bad(h, bad_assign); rc != FX_OK) return rc;
+    return *bad_assign > 0 ? km_bad_error(*bad_assign, h->ntotal) : FX_OK;
+}
+
+int fx_kmeans_profile_read(FxIndex* h, double* assign_ms, double* sort_ms, double* sum_ms, double* finish_ms) {
+    if (!h || !assign_ms || !sort_ms || !sum_ms || !finish_ms) return set_err(FX_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    HIP_TRY(hipStreamSynchronize(h->stream()));
+    double ms[4] = {0, 0, 0, 0};
+    float v = 0;
+    for (size_t i = 0; i + 3 < h->km_ev.size(); i += 4)
+        for (int p = 0; p < 3; ++p) {
+            HIP_TRY(hipEventElapsedTime(&v, h->km_ev[i + p], h->km_ev[i + p + 1]));
+            ms[p] += v;
+        }
+    for (size_t i = 0; i + 1 < h->km_ev_fin.size(); i += 2) {
+        HIP_TRY(hipEventElapsedTime(&v, h->km_ev_fin[i], h->km_ev_fin[i + 1]));
+        ms[3] += v;
+    }
+    for (hipEvent_t e : h->km_ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->km_ev_fin) (void)hipEventDestroy(e);
+    h->km_ev.clear();
+    h->km_ev_fin.clear();
+    *assign_ms = ms[0];
+    *sort_ms = ms[1];
+    *sum_ms = ms[2];
+    *finish_ms = ms[3];
     return FX_OK;
 }
 

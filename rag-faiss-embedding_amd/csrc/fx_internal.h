@@ -1,5 +1,5 @@
 // fx_internal.h -- shared between the HIP translation units (fx_kernels.hip,
-// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip) and the host C ABI
+// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip, fx_kmeans.hip) and the host C ABI
 // (fx_index.cpp): tiling constants, kernel parameter blocks, the launchers'
 // prototypes and their host-side helpers.  Not part of the public ABI
 // (include/fx_index.h).
@@ -415,6 +415,40 @@ hipError_t launch_subset_dist(int st_dt, int metric, const char* codes, int row_
                               hipStream_t s);
 // I[i] <- labels[I[i]] for rows 0 <= I[i] < ntotal, else -1
 hipError_t launch_label_ids(const int64_t* labels, int64_t ntotal, int64_t n, int64_t* I, hipStream_t s);
+// k-means (fx_kmeans.hip): one Lloyd update from (x, assign), bitwise
+// reproducible (fp64 sums in a fixed order, no floating-point atomics).
+constexpr int KM_M = 128;  // members of a cluster summed by one workgroup of k_km_sum
+struct KmUpdate {
+    const void* x;          // [n][d] dense rows on the device, dtype x_dt
+    int x_dt;
+    int64_t n;              // 1 .. 2^31-1 rows (one chunk)
+    int d;
+    int64_t k;              // clusters, 1 .. 2^31-1
+    const int64_t* assign;  // [n] cluster of every row; one outside [0, k) is counted in *bad and skipped
+    const float* dist;      // [n] the rows' distances (summed into obj), or null
+    double* sums;           // [k][d]
+    int64_t* counts;        // [k]
+    double* obj;            // one fp64
+    int accumulate;         // != 0: add to sums / counts / obj (an earlier chunk's), else overwrite
+    unsigned long long* bad;  // device counter of the skipped entries (never reset here)
+};
+// bytes of the workspace launch_km_update needs for a chunk of n rows
+hipError_t km_workspace(int64_t n, int64_t k, int d, size_t* bytes);
+// mid non-null: recorded between (keys, sort, segments) and (sum, fold)
+hipError_t launch_km_update(const KmUpdate& u, void* ws, size_t ws_bytes, hipStream_t s, hipEvent_t mid = nullptr);
+struct KmFinish {
+    const double* sums;     // [k][d]
+    const int64_t* counts;  // [k]
+    int64_t k;
+    int d;
+    const char* codes;      // the centroid index's stored rows (an empty cluster keeps its row)
+    int st_dt, row_bytes;
+    int spherical;          // != 0: every centroid L2-normalised
+    float* cent;            // out [k][d] fp32
+    int64_t* h;             // [k] scratch: the repair's working counts
+    int64_t* n_split;       // out: empty clusters repaired
+};
+hipError_t launch_km_finish(const KmFinish& f, hipStream_t s);
 // queries [n][d] (dtype q_dt, on the device) -> fp32 [n][kdim], zero padded (fx_hugek.hip: k_hk_queries)
 hipError_t launch_f32_queries(const void* q, int q_dt, int64_t n, int d, int kdim, float* out, hipStream_t s);
 // bits[0] <- max(bits[0], float bits of the largest of norms[0, n)) (atomicMax)

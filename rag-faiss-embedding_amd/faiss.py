@@ -25,6 +25,10 @@ as faiss``:
   and ``compute_distance_subset(x, labels) -> D`` (keys are the ids ``search``
   returns; one outside the index gives a NaN row / the missing slot's
   distance from device keys and raises from host keys);
+* ``Kmeans(d, k, ...)`` with ``train(x)`` / ``assign(x)``, ``centroids``,
+  ``obj``, ``iteration_stats`` and ``index``: k-means on the device over
+  numpy rows, device tensors or a flat index's stored rows, bitwise
+  reproducible;
 * ``write_index(index, path)`` / ``read_index(path)`` on the IxF2 format
   (IxM2 for a labelled index).
 
@@ -830,6 +834,250 @@ class IndexIDMap2(IndexIDMap):
 def _flat(index):
     """The flat index behind ``index`` (an ``IndexIDMap`` wraps one)."""
     return index.index if isinstance(index, IndexIDMap) else index
+
+
+# ---------------------------------------------------------------------------
+# faiss.Kmeans (include/fx_index.h "k-means")
+# ---------------------------------------------------------------------------
+KMEANS_CHUNK = 1 << 17  # rows per chunk of a k-means step (the library's default for "kmeans_chunk")
+
+
+def _is_index(x) -> bool:
+    return isinstance(x, (_FlatIndex, IndexIDMap))
+
+
+class Kmeans:
+    """``faiss.Kmeans``: Lloyd's algorithm on the GPU.  Every iteration is
+    ``fx_kmeans_step`` (the centroid index's own exact k = 1 search, then the
+    per-cluster fp64 sums, bitwise reproducible) and ``fx_kmeans_finish`` (the
+    new centroids, faiss's empty-cluster split with a deterministic donor, the
+    refill of the centroid index).
+
+    ``train(x)`` sets ``centroids`` (numpy ``(k, d)`` fp32), ``obj`` (numpy,
+    one value per iteration of the best redo), ``iteration_stats`` (a list of
+    ``{"obj", "nsplit"}``), ``counts`` (numpy int64: the cluster sizes of the
+    last iteration's assignment) and ``index``: an ``IndexFlatL2`` of this
+    module holding the centroids (``IndexFlatIP`` when ``spherical``), stored
+    in ``dtype``.
+
+    ``x`` is a numpy array, a device tensor (fp32 / bf16 / fp16: the whole
+    training is then stream-ordered, and ``obj``, ``nsplit`` and the count of
+    invalid assignments are read back once, at the end), or a flat index of
+    this module (``IndexFlatL2`` / ``IndexFlatIP``, or an ``IndexIDMap`` around
+    one): its stored rows are the training set, gathered chunk by chunk in the
+    storage dtype with ``reconstruct_batch`` on device keys, never through the
+    host.  (On a labelled index the keys are the labels: of rows that share a
+    label, the last one stands for all of them, as ``reconstruct`` has it.)
+
+    Seeding follows faiss -- the training rows of a set larger than ``k *
+    max_points_per_centroid`` are ``RandomState(seed).permutation(n)[:k *
+    max_points_per_centroid]``, the initial centroids of redo r the first k
+    rows of ``RandomState(seed + 1 + 15486557 * r).permutation(n_train)`` --
+    but the generator is numpy's, not faiss's own, so a faiss run with the
+    same seed starts from other rows.  The empty-cluster donor is the largest
+    cluster, where faiss draws it at random.  ``kmeans_chunk`` (0: the default
+    131,072) sets the rows per chunk of a step; the chunk order is part of the
+    summation order."""
+
+    def __init__(self, d: int, k: int, niter: int = 25, nredo: int = 1, verbose: bool = False,
+                 spherical: bool = False, seed: int = 1234, max_points_per_centroid: int = 256,
+                 min_points_per_centroid: int = 39, dtype: str = "float32", device: int = 0):
+        if dtype not in _DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(_DTYPES)}")
+        self.d, self.k = int(d), int(k)
+        self.niter, self.nredo = int(niter), int(nredo)
+        self.verbose, self.spherical, self.seed = bool(verbose), bool(spherical), int(seed)
+        self.max_points_per_centroid = int(max_points_per_centroid)
+        self.min_points_per_centroid = int(min_points_per_centroid)
+        self.dtype, self.device = dtype, int(device)
+        self.kmeans_chunk = 0
+        self.centroids = None
+        self.obj = np.empty(0, dtype=np.float64)
+        self.iteration_stats = []
+        self.counts = None
+        self.index = None
+
+    # -- the seeding rules (host only) --------------------------------------------
+    def _subsample_rows(self, n: int) -> Optional[np.ndarray]:
+        """The training rows of an n-row set: None (all of them), or the
+        subsample drawn when n > k * max_points_per_centroid."""
+        cap = self.k * self.max_points_per_centroid
+        if n <= cap:
+            return None
+        return np.random.RandomState(self.seed).permutation(n)[:cap].astype(np.int64)
+
+    def _init_rows(self, n_train: int, redo: int = 0) -> np.ndarray:
+        """The training rows that are redo ``redo``'s initial centroids."""
+        return np.random.RandomState(self.seed + 1 + 15486557 * redo).permutation(n_train)[:self.k].astype(np.int64)
+
+    def _chunk(self) -> int:
+        return self.kmeans_chunk if self.kmeans_chunk > 0 else KMEANS_CHUNK
+
+    # -- the training set ---------------------------------------------------------
+    def _size_of(self, x) -> int:
+        if _is_index(x):
+            assert x.d == self.d, "dimension mismatch"
+            return x.ntotal
+        assert len(x.shape) == 2 and x.shape[1] == self.d, "dimension mismatch"
+        return int(x.shape[0])
+
+    def _dev(self):
+        return _torch().device("cuda", self.device)
+
+    def _index_keys(self, x, rows: Optional[np.ndarray]):
+        """Device keys of the rows of index ``x`` (all, or ``rows``)."""
+        t = _torch()
+        flat = _flat(x)
+        n = flat.ntotal
+        if flat.has_ids:
+            keys = t.empty(n, dtype=t.int64, device=self._dev())
+            flat._bind_stream(True)
+            flat._check(flat._lib.fx_index_get_ids(flat._h, 0, n, ctypes.c_void_p(keys.data_ptr()), _lib.MEM_DEVICE))
+        else:
+            keys = t.arange(n, dtype=t.int64, device=self._dev()) + flat._id_offset
+        return keys if rows is None else keys[t.from_numpy(rows).to(self._dev())]
+
+    def _prepare(self, x, rows: Optional[np.ndarray]):
+        """(kind, data): "host" numpy rows, "device" tensor rows, or "index"
+        (flat index, device keys)."""
+        t = _torch()
+        if _is_index(x):
+            flat = _flat(x)
+            assert flat.device == self.device, f"index on cuda:{flat.device}, Kmeans on cuda:{self.device}"
+            keys = self._index_keys(x, rows)
+            if int(keys.numel()) <= self._chunk():  # one chunk: gathered once for all iterations
+                return "device", flat.reconstruct_batch(keys, dtype="storage")
+            return "index", (flat, keys)
+        if _is_device_tensor(x):
+            assert x.device.index == self.device, f"tensor on cuda:{x.device.index}, Kmeans on cuda:{self.device}"
+            _tensor_dtype(x)
+            if rows is not None:
+                x = x.index_select(0, t.from_numpy(rows).to(x.device))
+            return "device", x.contiguous()
+        x = np.asarray(x)
+        x = np.ascontiguousarray(x, dtype=np.float16 if x.dtype == np.float16 else np.float32)
+        return "host", (x if rows is None else np.ascontiguousarray(x[rows]))
+
+    def _take(self, kind, data, rows: np.ndarray):
+        """Rows ``rows`` of the prepared training set as a device tensor."""
+        t = _torch()
+        if kind == "index":
+            flat, keys = data
+            return flat.reconstruct_batch(keys[t.from_numpy(rows).to(self._dev())])
+        if kind == "device":
+            return data.index_select(0, t.from_numpy(rows).to(data.device))
+        return t.from_numpy(np.ascontiguousarray(data[rows], dtype=np.float32)).to(self._dev())
+
+    def _chunks(self, kind, data):
+        """The prepared training set as (pointer, rows, dtype code, mem, keep-alive) pieces."""
+        if kind == "host":
+            code = _lib.F16 if data.dtype == np.float16 else _lib.F32
+            yield ctypes.c_void_p(data.ctypes.data), data.shape[0], code, _lib.MEM_HOST, data
+        elif kind == "device":
+            yield ctypes.c_void_p(data.data_ptr()), data.shape[0], _tensor_dtype(data), _lib.MEM_DEVICE, data
+        else:
+            flat, keys = data
+            step = self._chunk()
+            for r0 in range(0, int(keys.numel()), step):
+                xc = flat.reconstruct_batch(keys[r0:r0 + step], dtype="storage")
+                yield ctypes.c_void_p(xc.data_ptr()), xc.shape[0], _tensor_dtype(xc), _lib.MEM_DEVICE, xc
+
+    def _new_index(self):
+        cls = IndexFlatIP if self.spherical else IndexFlatL2
+        ix = cls(self.d, dtype=self.dtype, device=self.device)
+        if self.kmeans_chunk > 0:
+            ix.set_option("kmeans_chunk", self.kmeans_chunk)
+        return ix
+
+    # -- faiss surface ------------------------------------------------------------
+    def train(self, x, weights=None, init_centroids=None) -> float:
+        """``Kmeans.train``: returns the final objective (the sum of the squared
+        distances of the last iteration's assignment; ``spherical``: of the
+        inner products)."""
+        if weights is not None:
+            raise NotImplementedError("Kmeans.train: weights are not supported")
+        n = self._size_of(x)
+        if n < self.k:
+            raise RuntimeError(f"Number of training points ({n}) should be at least as large as number of "
+                               f"clusters ({self.k})")
+        rows = self._subsample_rows(n)
+        n_train = n if rows is None else int(rows.size)
+        if n_train < self.k * self.min_points_per_centroid:
+            import warnings
+            warnings.warn(f"clustering {n_train} points to {self.k} centroids: please provide at least "
+                          f"{self.k * self.min_points_per_centroid} training points", RuntimeWarning, stacklevel=2)
+        if init_centroids is not None:
+            init_centroids = np.array(init_centroids, dtype=np.float32, order="C")
+            if init_centroids.shape != (self.k, self.d):
+                raise AssertionError(f"init_centroids must have shape ({self.k}, {self.d})")
+        t = _torch()
+        dev = self._dev()
+        kind, data = self._prepare(x, rows)
+        ix = self._new_index()
+        ix._bind_stream(True)
+        h = ix._h
+        niter, nredo = max(self.niter, 0), max(self.nredo, 1)
+        sums = t.empty((self.k, self.d), dtype=t.float64, device=dev)
+        counts = t.empty((nredo, self.k), dtype=t.int64, device=dev)
+        obj = t.zeros((nredo, max(niter, 1)), dtype=t.float64, device=dev)
+        nsplit = t.zeros((nredo, max(niter, 1)), dtype=t.int64, device=dev)
+        cents = t.empty((nredo, self.k, self.d), dtype=t.float32, device=dev)
+        ptr = lambda a: ctypes.c_void_p(a.data_ptr())  # noqa: E731
+        for redo in range(nredo):
+            if init_centroids is not None:
+                c0 = t.from_numpy(init_centroids).to(dev)
+            else:
+                c0 = self._take(kind, data, self._init_rows(n_train, redo)).to(t.float32)
+            if redo:
+                ix.reset()
+            ix.add(c0)
+            cents[redo].copy_(c0)
+            for it in range(niter):
+                for ci, (xp, nr, code, mem, _keep) in enumerate(self._chunks(kind, data)):
+                    ix._check(ix._lib.fx_kmeans_step(h, nr, xp, code, mem, None, None, ptr(sums), ptr(counts[redo]),
+                                                     ptr(obj[redo, it:]), 1 if ci else 0))
+                ix._check(ix._lib.fx_kmeans_finish(h, ptr(sums), ptr(counts[redo]), 1 if self.spherical else 0,
+                                                   ptr(cents[redo]), ptr(nsplit[redo, it:])))
+        # the one read-back: invalid assignments, objectives, repairs, centroids
+        bad = ctypes.c_int64(0)
+        ix._check(ix._lib.fx_kmeans_status(h, ctypes.byref(bad)))
+        obj_h, nsplit_h = obj.cpu().numpy()[:, :niter], nsplit.cpu().numpy()[:, :niter]
+        best = 0
+        if niter > 0 and nredo > 1:
+            final = obj_h[:, -1]
+            best = int(np.argmax(final) if self.spherical else np.argmin(final))
+            if best != nredo - 1:
+                ix.reset()
+                ix.add(cents[best])
+        self.index = ix
+        self.centroids = cents[best].cpu().numpy()
+        self.counts = counts[best].cpu().numpy() if niter > 0 else None
+        self.obj = obj_h[best].copy()
+        self.iteration_stats = [{"obj": float(o), "nsplit": int(s)} for o, s in zip(obj_h[best], nsplit_h[best])]
+        if self.verbose:
+            for i, st in enumerate(self.iteration_stats):
+                print(f"  Iteration {i} objective={st['obj']:g} nsplit={st['nsplit']}")
+        return float(self.obj[-1]) if niter > 0 else 0.0
+
+    def assign(self, x) -> Tuple:
+        """``Kmeans.assign``: ``(D, I)``, two 1-D arrays: the distance to and
+        the number of the nearest centroid of every row (numpy in -> numpy
+        out, a device tensor in -> device tensors out, an index in -> numpy,
+        in row order)."""
+        assert self.index is not None, "should train before assigning"
+        if not _is_index(x):
+            D, I = self.index.search(x, 1)
+            return D.reshape(-1), I.reshape(-1)
+        t = _torch()
+        flat, keys = _flat(x), self._index_keys(x, None)
+        n = int(keys.numel())
+        D = t.empty((n, 1), dtype=t.float32, device=keys.device)
+        I = t.empty((n, 1), dtype=t.int64, device=keys.device)
+        step = self._chunk()
+        for r0 in range(0, n, step):
+            xc = flat.reconstruct_batch(keys[r0:r0 + step], dtype="storage")
+            self.index.search(xc, 1, D=D[r0:r0 + step], I=I[r0:r0 + step])
+        return D.reshape(-1).cpu().numpy(), I.reshape(-1).cpu().numpy()
 
 
 def write_index(index, path: str) -> None:

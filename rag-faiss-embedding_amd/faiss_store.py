@@ -149,6 +149,23 @@ class FAISSVectorStore:
             logger.error("remove failed: %s", e)
             raise
 
+    def cluster(self, k: int, niter: int = 25, seed: int = 1234) -> Tuple[np.ndarray, np.ndarray]:
+        """Cluster the stored rows into ``k`` groups (extension; ``Kmeans`` of
+        the faiss surface trained on the index itself, so the rows never leave
+        the GPU).  Returns ``(centroids, labels)``: ``(k, d)`` fp32, and the
+        cluster of every stored row as numpy int64, in row order.  Errors are
+        logged and raised again, as in ``load_index``."""
+        try:
+            km = _fx.Kmeans(self.dimension, int(k), niter=int(niter), seed=int(seed), device=self.device)
+            km.train(self.index)
+            _, labels = km.assign(self.index)
+            logger.info("cluster: %d rows -> %d clusters, objective %g", self.index.ntotal, k,
+                        km.obj[-1] if len(km.obj) else 0.0)
+            return km.centroids, labels
+        except Exception as e:
+            logger.error("cluster failed: %s", e)
+            raise
+
     def save_index(self, filepath: Optional[str] = None):
         """faiss_store.py:83-97: IxF2 index file + pickle-protocol-4 id list
         at ``<path>.mapping``."""
