@@ -1,8 +1,8 @@
 // fx_internal.h -- shared between the HIP translation units (fx_kernels.hip,
 // fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip, fx_kmeans.hip) and the host C ABI
-// (fx_index.cpp): tiling constants, kernel parameter blocks, the launchers'
-// prototypes and their host-side helpers.  Not part of the public ABI
-// (include/fx_index.h).
+// (fx_index.cpp, fx_api_*.cpp, fx_plan.cpp; their own header: fx_host.h):
+// tiling constants, kernel parameter blocks, the launchers' prototypes and
+// their host-side helpers.  Not part of the public ABI (include/fx_index.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -161,7 +161,7 @@ constexpr int64_t RESCAN_MAX = 2048;
 // [c cap, min(n_flag[0], (c+1) cap)); device-gated like the fallbacks
 hipError_t launch_rescan_chunks(const int* n_flag, int cap, int nchunks, int* counts, hipStream_t s);
 
-// True on a thread that is capturing a search into a hipGraph (fx_index.cpp
+// True on a thread that is capturing a search into a hipGraph (fx_api_search.cpp
 // graph_build): the scan launchers then skip hipFuncSetAttribute, which the
 // do_search right before the capture has already applied for the same kernel.
 extern thread_local bool g_graph_capture;

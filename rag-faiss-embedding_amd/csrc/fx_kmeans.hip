@@ -1,6 +1,6 @@
 // fx_kmeans.hip -- the update half of Lloyd's algorithm on the device: faiss's
 // Clustering::train / faiss.Kmeans, given the assignment that a k = 1 search
-// over the centroid index returns (the other half: fx_index.cpp fx_kmeans_step).
+// over the centroid index returns (the other half: fx_api_kmeans.cpp fx_kmeans_step).
 //
 // Everything here is bitwise reproducible: the result depends only on
 // (x, assign, KM_M) and the order of the chunks, never on timing.  No floating

@@ -1,0 +1,87 @@
+// fx_plan.h -- the launch planners (fx_plan.cpp): pure integer logic over an
+// index's shape (IndexShape) and options.  They decide every grid shape and
+// chunk plan the host launches, make no HIP call, and are checked against a
+// golden on the CPU (tests/test_plan_golden.py).
+#pragma once
+#include "fx_host.h"
+
+namespace fx {
+
+// split count whose live workgroups (one per CU: the scan's LDS) fill whole
+// rounds of 256 CUs best, with >= ~4 rounds and >= min_tiles tiles per split
+int fill_splits(int live_tiles, int eff_tiles, int n_ctiles, int min_tiles);
+
+// The shape-only part of a scan's grid (map_tile's fields), for ntl query
+// tiles and nct corpus tiles with >= min_tiles tiles per split.  partition:
+// corpus-partitioned placement is admissible (taken once every XCD gets
+// min_tiles tiles); group_qtiles: placement 0 gives each XCD a fixed group of
+// query tiles when there are >= 8.  No index and no option enters.
+struct SplitPlan {
+    int place, sx, splits, qt_per_xcd;
+    int qslots;  // workgroups per split: ntl, or 8 qt_per_xcd
+    void store(ScanParams& p) const {
+        p.place = place;
+        p.sx = sx;
+        p.splits = splits;
+        p.qt_per_xcd = qt_per_xcd;
+        p.grid = qslots * splits;
+    }
+};
+SplitPlan plan_splits(int ntl, int nct, int min_tiles, bool partition, bool group_qtiles);
+
+// The scan's grid (fx_plan.cpp has the reasoning at each definition).  v5_qt:
+// k_scan_v5's query tile for the rows' scan dtype (scan_v5_qt; 0: it has no
+// shape for them) -- passed in, so that this file needs no kernel object.
+void plan_scan(const IndexShape& ix, const Options& o, int64_t nq, int k, int v5_qt, ScanParams& p);
+void plan_sel_scan(const IndexShape& ix, int64_t nq, int k, ScanParams& p);
+void plan_range_scan(const IndexShape& ix, int64_t nq, ScanParams& p);
+int big_k1(int k);
+bool small_many(int k, int64_t nq, int splits);
+// which scan image the shape (dtype, row_bytes, metric) and options call for
+int image_kind(const IndexShape& ix, const Options& o);
+
+// Host-output searches (the reference's call form) return through ONE packed
+// device buffer, copied back with one D2H:
+//   [D: nq k f32 | I: nq k i64 | n_drop | n_flag | flag list: nq i32]
+// (the copy covers D .. n_flag; the flag list stays on the device for the
+// fallback chain)
+struct HostOut {
+    size_t offI = 0, offW = 0, copy_bytes = 0, bytes = 0;
+};
+HostOut host_out_layout(int64_t nq, int k);
+
+// ---- remove_ids (fx_remove.hip): the host's chunk plan ----------------------
+
+// Kept rows before row r, for the rows the plan asks about: any row (the
+// prefix and mask words on the host; only for a staging buffer smaller than
+// RM_GROUP_ROWS rows) or the multiples of RM_GROUP_ROWS, the first removed
+// row and ntotal (the device's gp words).
+struct KeptPrefix {
+    int64_t ntotal = 0, first = 0, kept = 0;
+    int64_t g = RM_GROUP_ROWS;  // the plan's boundary granule: RM_GROUP_ROWS (gp) or 1 (words + mask)
+    std::vector<unsigned> gp, words, mask;
+    int64_t at(int64_t r) const {
+        if (r >= ntotal) return kept;
+        if (r <= first) return r;  // no row below the first removed one is removed
+        if (g == 1) return (int64_t)words[r >> 5] + __builtin_popcount(~mask[r >> 5] & ((1u << (r & 31)) - 1u));
+        return gp[r / RM_GROUP_ROWS];
+    }
+};
+
+struct RemoveChunk {
+    int64_t s0, s1;  // source rows
+    int64_t d0, kept;  // its kept rows go to rows [d0, d0 + kept)
+    bool direct;     // d0 + kept <= s0: moved in place by one launch; else gathered into staging, then copied
+};
+
+// Ascending chunks of source rows from the first removed row to ntotal, cut at
+// multiples of P.g.  From s0 (kept rows before it: d0) the candidates are the
+// longest direct chunk (the largest boundary s1 with prefix(s1) <= s0) and the
+// longest staged one (prefix(s1) - d0 <= stage_rows); the direct one is taken
+// when it is at least half as long (a staged row moves twice), so small
+// shifts do not turn into many small launches.  Chunks without a kept row are
+// skipped.  false: a boundary step holds more kept rows than the staging
+// buffer (never: the caller picks g <= stage_rows).
+bool plan_remove(const KeptPrefix& P, int64_t stage_rows, std::vector<RemoveChunk>& out);
+
+}  // namespace fx

@@ -6,7 +6,7 @@
 // `codes` and `norms` where they lie.  Every destination row is at or below
 // its source row, so a workgroup writing row j could destroy a source row
 // that another has not read yet.  The order comes from the stream, never from
-// workgroups waiting on each other: the host (fx_index.cpp remove_rows) cuts
+// workgroups waiting on each other: the host (fx_api_remove.cpp remove_rows) cuts
 // the rows from the first removed one upward into ascending chunks of source
 // rows, one k_move_rows launch each, and a launch only ever writes
 //   - below the first source row of its chunk (a "direct" chunk: its

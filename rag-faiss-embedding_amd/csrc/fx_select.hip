@@ -1,7 +1,7 @@
 // fx_select.hip -- filtered search: faiss's IDSelector on the flat index.
 //
 // faiss: index.search(x, k, params=SearchParameters(sel=IDSelector...)) ranks
-// only the rows the selector admits.  Here a selector (FxSelector, fx_index.cpp)
+// only the rows the selector admits.  Here a selector (FxSelector, fx_host.h)
 // is a device image of the admitted subset of an index's rows [0, ntotal):
 //
 //   row mask     one bit per local row (bit r & 31 of word r >> 5), 4 words

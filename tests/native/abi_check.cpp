@@ -1,7 +1,7 @@
 // abi_check.cpp -- host-sanitizer driver of the C ABI (include/fx_index.h).
 //
 // Built by `make -C rag-faiss-embedding_amd/csrc asan` with the host C++ of
-// fx_index.cpp compiled under -fsanitize=address,undefined (device code as
+// fx_index.cpp, fx_api_*.cpp and fx_plan.cpp compiled under -fsanitize=address,undefined (device code as
 // usual: GPU sanitizers are not available on this pool), and run on the GPU
 // box by tests/test_native_asan.py.  It walks every entry point through the
 // paths that size host / device buffers by hand: growth by repeated adds,

@@ -1,5 +1,5 @@
 """Host-sanitizer run of the stable-id calls of the C ABI:
-tests/native/idmap_check.cpp linked against fx_index.cpp built with
+tests/native/idmap_check.cpp linked against the host C++ (fx_index.cpp, fx_api_*.cpp, fx_plan.cpp) built with
 -fsanitize=address,undefined on the host side (`make -C
 rag-faiss-embedding_amd/csrc asan`, also run by __graft_entry__.build()), the
 way tests/test_native_asan.py runs abi_check.  The driver walks

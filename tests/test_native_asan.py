@@ -1,5 +1,5 @@
 """Host-sanitizer run of the C ABI ("Race detection /
-sanitizers"): tests/native/abi_check.cpp linked against fx_index.cpp built
+sanitizers"): tests/native/abi_check.cpp linked against the host C++ (fx_index.cpp, fx_api_*.cpp, fx_plan.cpp) built
 with -fsanitize=address,undefined on the host side (`make -C
 rag-faiss-embedding_amd/csrc asan`, also run by __graft_entry__.build()).  The
 driver exercises every entry point of include/fx_index.h -- ragged growth,

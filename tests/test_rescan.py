@@ -1,4 +1,4 @@
-"""The re-scan of uncertified queries (fx_index.cpp plan_rescan): queries
+"""The re-scan of uncertified queries (fx_api_search.cpp plan_rescan): queries
 whose top-k the scan's KP-candidate lists cannot certify are scanned again
 with a wide candidate set (k_refine_big over k1 = max(512, 4k) candidates)
 before anything falls to the exact fp64 scan of every row.

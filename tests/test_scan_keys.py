@@ -2,7 +2,7 @@
 
 The search results are exact even when a scan key is wrong: the refine
 recomputes distances exactly and an uncertified query falls back to the exact
-scan (fx_index.cpp do_search).  So end-to-end parity alone cannot pin the scan
+scan (fx_api_search.cpp do_search).  So end-to-end parity alone cannot pin the scan
 kernel.  Here the scan's whole key matrix is dumped (FX_SCAN_DBG=32 ->
 FX_SCAN_KEYS) and compared with a float64 restatement of the same operands:
 
