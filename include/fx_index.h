@@ -35,6 +35,9 @@
  *   index.compute_        (re-scoring a candidate    faiss_IndexFlat_compute_     fx_index_compute_distance_subset
  *     distance_subset      set from elsewhere)        distance_subset
  *   (is it an IDMap?)     --                         faiss_IndexIDMap_cast        fx_index_has_ids
+ *   IndexIVFFlat(q, d,    (a search over nprobe of   faiss_IndexIVFFlat_new_with  fx_ivf_create, fx_ivf_add,
+ *     nlist)               nlist inverted lists; see  _metric                      fx_ivf_search
+ *                          "inverted file" below)
  *   index.ntotal          faiss_store.py:53          faiss_Index_ntotal           fx_index_ntotal
  *   (re)IndexFlatL2(d)    faiss_store.py:126         faiss_Index_reset            fx_index_reset
  *   faiss.write_index     faiss_store.py:91,         faiss_write_index_fname      fx_index_write
@@ -514,6 +517,108 @@ int fx_kmeans_status(FxIndex* centroids, int64_t* bad_assign);
  * searches, key build + sort + segments, sum + fold, and the finishes. */
 int fx_kmeans_profile_read(FxIndex* centroids, double* assign_ms, double* sort_ms, double* sum_ms,
                            double* finish_ms);
+
+/* ---- inverted file: faiss IndexIVFFlat ---------------------------------------
+ *
+ *   faiss (Python)                      faiss C++ / C API                               this ABI
+ *   IndexIVFFlat(quantizer, d, nlist)   faiss_IndexIVFFlat_new_with_metric              fx_ivf_create
+ *   index.is_trained                    faiss_Index_is_trained                          (quantizer ntotal == nlist)
+ *   index.train(x)                      faiss_Index_train                               the k-means calls above, then
+ *                                                                                       fx_index_add on the quantizer
+ *   index.add(x) / add_with_ids(x, ids) faiss_Index_add / faiss_Index_add_with_ids      fx_ivf_add
+ *   index.nprobe; index.search(x, k)    faiss_IndexIVF_set_nprobe / faiss_Index_search  fx_ivf_search
+ *   index.reset()                       faiss_Index_reset                               fx_ivf_reset
+ *   index.ntotal                        faiss_Index_ntotal                              fx_ivf_ntotal
+ *   invlists.list_size(l)               faiss_IndexIVF_get_list_size                    fx_ivf_list_sizes
+ *   invlists.get_ids(l)                 faiss_IndexIVF_invlists_get_ids                 fx_ivf_list_ids
+ *   (GC of the index)                   faiss_Index_free                                fx_ivf_free
+ *
+ * The quantizer is an unlabelled flat index with id offset 0 on the same
+ * device, BORROWED: the caller keeps it alive as long as the IVF index.  The
+ * index is trained as soon as the quantizer holds nlist rows (the centroids),
+ * however they got there; an add or a search before that is FX_E_ARG.
+ *
+ * Row i of an add goes to list quantizer.search(x_i, 1): the quantizer's own
+ * metric and tie rule (the smaller centroid number).  Rows are stored in the
+ * storage dtype exactly as the flat index stores them, in LIST ORDER: list l
+ * owns a run of rows, in insertion order.  An add appends to the tail and the
+ * next search (or list accessor) regroups: a stable device sort of
+ * list << 32 | row keys and a gather into second buffers, which needs a
+ * second copy of the rows while it runs (released once the buffers are
+ * swapped) and is O(ntotal) per add-then-search cycle (merging only the tail
+ * is future work), and reads the longest list's length
+ * back to the host once (the one synchronisation of a search after an add).
+ *
+ * A search probes, per query, the min(nprobe, nlist) lists of
+ * quantizer.search(q, nprobe), and returns the k best rows among them under
+ * the index metric, ranked by (exact fp32 distance, list number, insertion
+ * order within the list), i.e. by position in the list-ordered store (faiss's
+ * own IVF tie order is an artefact of its heap).  Within the probed lists the
+ * result is exact as the flat index's is: ids bit-exact, distances the fp64 sum
+ * rounded once; with nprobe = nlist it is the flat index's result (up to the
+ * tie rule).  Missing slots: I = -1, D = +-FLT_MAX.  I holds the ids of
+ * fx_ivf_add: sequential from 0 in insertion order when ids was NULL, else the
+ * caller's int64 (any value, duplicates included); the two may not be mixed on
+ * a non-empty index (FX_E_ARG, as fx_index_add / fx_index_add_with_ids).
+ *
+ * Errors: FX_E_ARG for a null handle, d different from the quantizer's,
+ * nlist < 1, a labelled quantizer or one with an id offset, add or search on an
+ * untrained index, k < 1, nprobe < 1, a bad dtype or mem; FX_E_UNSUPPORTED for
+ * k > FX_MAX_K, nq * nprobe >= 2^31, min(nprobe, nlist) > FX_MAX_K (the coarse
+ * search's k), ntotal >= 2^31; FX_E_INTEGRITY when a row was assigned outside
+ * [0, nlist) (it belongs to no list; counted as k-means counts them) and for a
+ * host-output search whose candidate lists or probe lists held ids outside the
+ * index (never in a correct build).  nq == 0 and n == 0 are FX_OK.
+ *
+ * Out of scope: writing / reading an IVF index (faiss's "IwFl" layout cannot
+ * be checked here: persist the quantizer as IxF2 and re-add the rows),
+ * remove_ids, range_search, selectors, reconstruct*, search_preassigned,
+ * sharding across GPUs, the search graph, IndexIVFPQ /
+ * IndexIVFScalarQuantizer. */
+typedef struct FxIvf FxIvf;
+int fx_ivf_create(FxIndex* quantizer, int d, int64_t nlist, int storage_dtype, int metric, FxIvf** out);
+void fx_ivf_free(FxIvf* ivf);
+/* ids NULL: sequential ids ntotal .. ntotal + n - 1.  Device x (and ids) is
+ * stream-ordered; host x blocks. */
+int fx_ivf_add(FxIvf* ivf, int64_t n, const void* x, int x_dtype, int x_mem, const int64_t* ids, int ids_mem);
+/* Host results block; device queries and results are stream-ordered (the first
+ * search after an add synchronises once for the regroup).  k <= 32: the fused
+ * path (MFMA list scan, exact refine, exact fallback for uncertified queries,
+ * all decided on the device); 32 < k <= FX_MAX_K: the exact list scan.
+ * Limitation: the refine certifies a query from the room between its k-th and
+ * its 32nd candidate key, so as k nears 32 more queries are uncertified, and at
+ * k = 32 every query whose probed lists hold 32 rows or more is; those are
+ * re-ranked by the exact list scan (one thread per row, fp64), which is
+ * correct but much slower than the MFMA path.  Fast for small k (k = 10: none
+ * flagged on the test and benchmark corpora); a wider candidate set for k near
+ * 32, as the flat index's re-scan has, is future work. */
+int fx_ivf_search(FxIvf* ivf, int64_t nq, const void* q, int q_dtype, int q_mem, int k, int nprobe,
+                  float* D, int64_t* I, int out_mem);
+/* Empties the lists, keeps the quantizer (and so the training). */
+int fx_ivf_reset(FxIvf* ivf);
+int fx_ivf_ntotal(const FxIvf* ivf, int64_t* out);
+/* out: host [nlist]. */
+int fx_ivf_list_sizes(FxIvf* ivf, int64_t* out);
+/* *n = rows of `list`; out (host, cap entries; may be NULL with cap 0)
+ * receives the first min(*n, cap) ids in insertion order. */
+int fx_ivf_list_ids(FxIvf* ivf, int64_t list, int64_t* out, int64_t cap, int64_t* n);
+int fx_ivf_set_stream(FxIvf* ivf, void* stream);
+/* Of the last search (after a device-output one this synchronises): queries the
+ * refine could not certify (re-ranked by the exact list scan, so both counts
+ * are equal), and candidate / probe ids outside the index (0 in a correct
+ * build). */
+int fx_ivf_last_counts(FxIvf* ivf, int64_t* fallbacks, int64_t* exact_fallbacks, int64_t* dropped);
+/* With profiling on, every pass of a search records events around its parts;
+ * _read waits and returns the milliseconds summed since the last read: the
+ * coarse search, pairs + query preparation, the list scan (exact path: the
+ * exact scan), refine + exact fallback, and the passes they cover. */
+int fx_ivf_profile(FxIvf* ivf, int enable);
+int fx_ivf_profile_read(FxIvf* ivf, double* coarse_ms, double* pairs_ms, double* scan_ms, double* refine_ms,
+                        int64_t* passes);
+/* The plan of the last search: path 0 fused / 1 exact, tile chunks per list,
+ * candidate slots per query (nprobe * chunks), queries per pass, and the list
+ * scan's launch-grid bound. */
+int fx_ivf_last_plan(FxIvf* ivf, int* path, int* chunks, int* slots, int64_t* q_batch, int64_t* grid);
 
 /* faiss.write_index / faiss.read_index on the IxF2 format (faiss_store.py:
  * 91,106): fourcc "IxF2", i32 d, i64 ntotal, i64 1<<20, i64 1<<20,

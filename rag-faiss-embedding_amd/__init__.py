@@ -3,8 +3,8 @@ luzbetak/rag-faiss-embedding.
 
 Surfaces (each mirrors the reference interface it replaces):
 
-* :mod:`.faiss`          -- ``IndexFlatL2`` / ``IndexFlatIP`` / ``write_index`` /
-                            ``read_index`` (faiss-cpu as called at
+* :mod:`.faiss`          -- ``IndexFlatL2`` / ``IndexFlatIP`` / ``IndexIVFFlat`` /
+                            ``write_index`` / ``read_index`` (faiss-cpu as called at
                             faiss_store.py:29-126, rag_datastore_manager.py:138-218)
 * :mod:`.faiss_store`    -- ``FAISSVectorStore`` (faiss_store.py:10-128)
 * :mod:`.vectorization`  -- ``VectorizationPipeline`` (vectorization.py:10-47)

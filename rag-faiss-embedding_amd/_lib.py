@@ -82,6 +82,20 @@ SIGNATURES = {
     "fx_kmeans_finish": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "fx_kmeans_status": (_i, [_vp, ctypes.POINTER(_i64)]),
     "fx_kmeans_profile_read": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 4),
+    "fx_ivf_create": (_i, [_vp, _i, _i64, _i, _i, _pp]),
+    "fx_ivf_free": (None, [_vp]),
+    "fx_ivf_add": (_i, [_vp, _i64, _vp, _i, _i, _vp, _i]),
+    "fx_ivf_search": (_i, [_vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _i]),
+    "fx_ivf_reset": (_i, [_vp]),
+    "fx_ivf_ntotal": (_i, [_vp, ctypes.POINTER(_i64)]),
+    "fx_ivf_list_sizes": (_i, [_vp, _vp]),
+    "fx_ivf_list_ids": (_i, [_vp, _i64, _vp, _i64, ctypes.POINTER(_i64)]),
+    "fx_ivf_set_stream": (_i, [_vp, _vp]),
+    "fx_ivf_last_counts": (_i, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "fx_ivf_profile": (_i, [_vp, _i]),
+    "fx_ivf_profile_read": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(_i64)]),
+    "fx_ivf_last_plan": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64),
+                              ctypes.POINTER(_i64)]),
     "fx_index_write": (_i, [_vp, ctypes.c_char_p]),
     "fx_index_read": (_i, [ctypes.c_char_p, _i, _i, _pp]),
     "fx_merge_shards": (_i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -1,0 +1,587 @@
+// fx_api_ivf.cpp -- inverted file (fx_ivf.hip): fx_ivf_create / _add / _search and the accessors.
+//
+// The payload (FxIvf::pay) is a labelled flat index this file drives directly:
+// rows and labels are appended to its tail by fx_index_add_with_ids, each new
+// row's list is recorded from the quantizer's k = 1 search, and the next search
+// regroups the rows into list order (a stable sort of list << 32 | row keys and a
+// gather into second buffers that are then swapped in).  The regroup needs a
+// second copy of the payload while it runs (released again once the buffers
+// are swapped) and is O(ntotal) per add-then-search cycle; merging only the
+// appended tail is future work.
+#include "fx_host.h"
+#include "fx_plan.h"
+
+using namespace fx;
+
+namespace {
+
+// The quantizer's searches run on the payload's stream for the duration of a
+// call (the quantizer locked): both directions ordered on the device, as
+// fx_index_set_stream orders a switch.
+struct BorrowQuant {
+    FxIndex* q;
+    hipStream_t s, prev_user, prev;
+    std::unique_lock<std::mutex> lk;
+    BorrowQuant(FxIndex* quant, hipStream_t stream) : q(quant), s(stream), lk(quant->mu) {
+        prev_user = q->user_stream;
+        prev = q->stream();
+    }
+    hipError_t begin() {
+        hipError_t e = hipSuccess;
+        if (prev != s) {
+            e = hipEventRecord(q->switch_ev, prev);
+            if (e == hipSuccess) e = hipStreamWaitEvent(s, q->switch_ev, 0);
+        }
+        q->user_stream = s;
+        return e;
+    }
+    ~BorrowQuant() {
+        q->user_stream = prev_user;
+        if (prev != s && hipEventRecord(q->switch_ev, s) == hipSuccess) (void)hipStreamWaitEvent(prev, q->switch_ev, 0);
+    }
+};
+
+int ivf_trained(const FxIvf* v, const char* who) {
+    if (v->quant->ntotal != v->nlist)
+        return set_err(FX_E_ARG, "%s: the index is not trained (the quantizer holds %lld of %lld centroids)", who,
+                       (long long)v->quant->ntotal, (long long)v->nlist);
+    return FX_OK;
+}
+
+// buf holds at least `want` bytes, its first `keep` bytes carried over
+hipError_t grow_keep(DevBuf& buf, size_t want, size_t keep, hipStream_t s) {
+    if (want <= buf.bytes) return hipSuccess;
+    DevBuf nb;
+    hipError_t e = nb.ensure(std::max(want, buf.bytes + buf.bytes / 2));
+    if (e != hipSuccess) return e;
+    if (buf.p && keep > 0) e = hipMemcpyAsync(nb.p, buf.p, keep, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // (work in flight still reads the old buffer)
+    if (e != hipSuccess) return e;
+    buf.swap(nb);
+    return hipSuccess;
+}
+
+int ivf_bad_error(int64_t bad, int64_t nlist) {
+    return set_err(FX_E_INTEGRITY, "ivf: %lld rows were assigned outside [0, %lld) and belong to no list", (long long)bad,
+                   (long long)nlist);
+}
+
+// the skipped-assignment count since the last read (the stream synchronised by the caller's copy), then 0 again
+int ivf_read_bad(FxIvf* v, int64_t* out) {
+    hipStream_t s = v->pay->stream();
+    unsigned long long bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, v->bad, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(v->bad, 0, 8, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = (int64_t)bad;
+    return FX_OK;
+}
+
+// the payload in list order (a no-op unless rows were added since)
+int ivf_regroup(FxIvf* v) {
+    if (!v->dirty) return FX_OK;
+    FxIndex* p = v->pay;
+    hipStream_t s = p->stream();
+    const int64_t n = p->ntotal;
+    v->h_off.assign((size_t)v->nlist + 1, 0);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(v->list_off, 0, (size_t)(v->nlist + 1) * 4, s));
+        v->max_list_rows = 0;
+        v->dirty = false;
+        return FX_OK;
+    }
+    HIP_TRY(v->codes_alt.ensure((size_t)p->cap_rows * p->row_bytes));
+    HIP_TRY(v->norms_alt.ensure((size_t)p->cap_rows * 4));
+    HIP_TRY(v->labels_alt.ensure(std::max<size_t>((size_t)p->cap_rows * 8, p->idm.labels.bytes)));
+    HIP_TRY(v->row_list_alt.ensure(std::max<size_t>((size_t)p->cap_rows * 4, v->row_list.bytes)));
+    size_t ws = 0;
+    HIP_TRY(ivf_regroup_bytes(n, v->nlist, &ws));
+    HIP_TRY(v->rws.ensure(ws));
+    IvfRegroup r{};
+    r.n = n;
+    r.nlist = v->nlist;
+    r.row_bytes = p->row_bytes;
+    r.codes = p->codes;
+    r.norms = p->norms;
+    r.labels = p->idm.labels;
+    r.row_list = v->row_list;
+    r.dst_codes = v->codes_alt;
+    r.dst_norms = v->norms_alt;
+    r.dst_labels = v->labels_alt;
+    r.dst_row_list = v->row_list_alt;
+    r.list_off = v->list_off;
+    r.max_rows = v->max_rows;
+    HIP_TRY(launch_ivf_regroup(r, v->rws.p, v->rws.bytes, s));
+    // the one synchronisation: the longest list (the planner's input), with the lists' offsets
+    int max_rows = 0;
+    HIP_TRY(hipMemcpyAsync(&max_rows, v->max_rows, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(v->h_off.data(), v->list_off, (size_t)(v->nlist + 1) * 4, hipMemcpyDeviceToHost, s));
+    int64_t bad = 0;
+    if (const int rc = ivf_read_bad(v, &bad); rc != FX_OK) return rc;
+    // (the stream is idle: nothing reads the buffers that go out)
+    p->codes.swap(v->codes_alt);
+    p->norms.swap(v->norms_alt);
+    p->idm.labels.swap(v->labels_alt);
+    v->row_list.swap(v->row_list_alt);
+    // the second copy goes again: device memory is back at one payload
+    v->codes_alt.release();
+    v->norms_alt.release();
+    v->labels_alt.release();
+    v->row_list_alt.release();
+    v->max_list_rows = max_rows;
+    v->dirty = false;
+    if (bad > 0) return ivf_bad_error(bad, v->nlist);
+    return FX_OK;
+}
+
+int ivf_read_counts(FxIvf* v) {
+    if (v->counts_pending) {
+        DeviceGuard g(v->pay->device);
+        HIP_TRY(hipStreamSynchronize(v->pay->stream()));
+        v->last_dropped = v->pin_cnt[0];
+        v->last_fallbacks = v->pin_cnt[1];
+        v->last_bad_probe = v->pin_cnt[2];
+        v->counts_pending = false;
+        // the borrowed coarse search's own integrity count (of the last pass; its copies ran on this stream)
+        std::lock_guard<std::mutex> ql(v->quant->mu);
+        if (const int rc = read_counts(v->quant); rc != FX_OK) return rc;
+    }
+    return FX_OK;
+}
+
+int ivf_integrity(const FxIvf* v) {
+    return set_err(FX_E_INTEGRITY,
+                   "ivf search: %lld candidate row ids outside [0, %lld) were dropped, %lld probed list numbers lay "
+                   "outside [0, %lld)",
+                   (long long)v->last_dropped, (long long)v->pay->ntotal, (long long)v->last_bad_probe,
+                   (long long)v->nlist);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fx_ivf_create(FxIndex* quantizer, int d, int64_t nlist, int storage_dtype, int metric, FxIvf** out) {
+    if (!out) return set_err(FX_E_ARG, "null out");
+    *out = nullptr;
+    if (nlist < 1) return set_err(FX_E_ARG, "ivf: nlist must be positive (got %lld)", (long long)nlist);
+    if (nlist >= (int64_t)INT32_MAX) return set_err(FX_E_UNSUPPORTED, "ivf: more than 2^31-2 lists");
+    if (!quantizer) return set_err(FX_E_ARG, "ivf: null quantizer");
+    if (quantizer->d != d)
+        return set_err(FX_E_ARG, "ivf: the quantizer has d = %d, the index d = %d", quantizer->d, d);
+    if (quantizer->has_ids) return set_err(FX_E_ARG, "ivf: the quantizer carries labels (add_with_ids)");
+    if (quantizer->id_offset != 0)
+        return set_err(FX_E_ARG, "ivf: the quantizer has id offset %lld", (long long)quantizer->id_offset);
+    FxIndex* pay = nullptr;
+    if (const int rc = fx_index_create(d, storage_dtype, metric, quantizer->device, &pay); rc != FX_OK) return rc;
+    FxIvf* v = new FxIvf();
+    v->quant = quantizer;
+    v->pay = pay;
+    v->nlist = nlist;
+    v->h_off.assign((size_t)nlist + 1, 0);
+    DeviceGuard g(pay->device);
+    hipError_t e = v->list_off.ensure((size_t)(nlist + 1) * 4);
+    if (e == hipSuccess) e = hipMemset(v->list_off, 0, (size_t)(nlist + 1) * 4);
+    if (e == hipSuccess) e = v->max_rows.ensure(16);
+    if (e == hipSuccess) e = v->bad.ensure(8);
+    if (e == hipSuccess) e = hipMemset(v->bad, 0, 8);
+    if (e == hipSuccess) e = v->cnt.ensure(16);
+    if (e == hipSuccess) e = hipMemset(v->cnt, 0, 16);
+    if (e == hipSuccess) e = v->pin_cnt.ensure(16);
+    if (e != hipSuccess) {
+        fx_ivf_free(v);
+        return set_err(FX_E_HIP, "ivf init: %s", hipGetErrorString(e));
+    }
+    v->pin_cnt[0] = v->pin_cnt[1] = v->pin_cnt[2] = 0;
+    *out = v;
+    return FX_OK;
+}
+
+void fx_ivf_free(FxIvf* v) {
+    if (!v) return;
+    FxIndex* pay = v->pay;
+    {
+        DeviceGuard g(pay->device);
+        (void)hipStreamSynchronize(pay->stream());
+        for (hipEvent_t e : v->ev) (void)hipEventDestroy(e);
+        v->pay = nullptr;
+        delete v;  // its buffers, with the device current
+    }
+    fx_index_free(pay);
+}
+
+int fx_ivf_add(FxIvf* v, int64_t n, const void* x, int x_dtype, int x_mem, const int64_t* ids, int ids_mem) {
+    // (the handle last: the other checks are then reachable without a device)
+    if (n < 0) return set_err(FX_E_ARG, "negative n");
+    if (!check_dtype(x_dtype)) return set_err(FX_E_ARG, "bad x dtype %d", x_dtype);
+    if (!valid_mem(x_mem)) return set_err(FX_E_ARG, "bad x_mem %d", x_mem);
+    if (ids && !valid_mem(ids_mem)) return set_err(FX_E_ARG, "bad ids_mem %d", ids_mem);
+    if (!v) return set_err(FX_E_ARG, "null ivf index");
+    if (n == 0) return FX_OK;
+    if (!x) return set_err(FX_E_ARG, "null x");
+    std::lock_guard<std::mutex> lk(v->mu);
+    if (const int rc = ivf_trained(v, "ivf add"); rc != FX_OK) return rc;
+    FxIndex* p = v->pay;
+    if (p->ntotal > 0 && v->sequential && ids)
+        return set_err(FX_E_ARG, "add_with_ids not implemented for an index that holds rows without labels");
+    if (p->ntotal > 0 && !v->sequential && !ids)
+        return set_err(FX_E_ARG, "add does not make sense on an index with labels: use add_with_ids");
+    if (p->ntotal + n + TILE_R >= (int64_t)INT32_MAX)
+        return set_err(FX_E_UNSUPPORTED, "ivf: more than 2^31-1 rows");
+    DeviceGuard g(p->device);
+    if (!g.ok) return set_err(FX_E_HIP, "hipSetDevice(%d) failed", p->device);
+    hipStream_t s = p->stream();
+    // a list's last tile may start up to 127 rows before the list's end: the
+    // arrays hold a whole tile past the last row
+    if (const int rc = fx_index_reserve(p, p->ntotal + n + TILE_R); rc != FX_OK) return rc;
+    HIP_TRY(grow_keep(v->row_list, (size_t)p->cap_rows * 4, (size_t)p->ntotal * 4, s));
+
+    // the new rows' lists: the quantizer's k = 1 search, chunk by chunk
+    const int64_t rowb = (int64_t)p->d * dtype_size(x_dtype);
+    const int64_t chunk = std::min<int64_t>(n, v->quant->opt.kmeans_chunk > 0 ? v->quant->opt.kmeans_chunk
+                                                                               : (int)KMEANS_CHUNK_DEFAULT);
+    HIP_TRY(v->assign.ensure((size_t)chunk * 12));
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int64_t nr = std::min(chunk, n - r0);
+        int64_t* a = (int64_t*)v->assign.p;
+        float* dd = (float*)((char*)v->assign.p + (size_t)chunk * 8);
+        {
+            BorrowQuant bq(v->quant, s);
+            HIP_TRY(bq.begin());
+            const int rc = do_search(v->quant, nr, (const char*)x + r0 * rowb, x_dtype, x_mem, 1, dd, a, FX_MEM_DEVICE);
+            if (rc != FX_OK) return rc;
+        }
+        HIP_TRY(launch_ivf_record(a, nr, v->nlist, v->row_list + p->ntotal + r0, v->bad, s));
+    }
+    // rows and labels to the payload's tail
+    const int64_t* dids = ids;
+    int dmem = ids_mem;
+    if (!ids) {
+        HIP_TRY(v->ids.ensure((size_t)n * 8));
+        HIP_TRY(launch_ivf_iota((int64_t*)v->ids.p, n, p->ntotal, s));
+        dids = (const int64_t*)v->ids.p;
+        dmem = FX_MEM_DEVICE;
+    }
+    const bool first = p->ntotal == 0;
+    if (const int rc = fx_index_add_with_ids(p, n, x, x_dtype, x_mem, dids, dmem); rc != FX_OK) return rc;
+    if (first) v->sequential = ids == nullptr;
+    v->dirty = true;
+    if (x_mem == FX_MEM_HOST) {  // a host call waits for its work: its skipped rows are known now
+        int64_t bad = 0;
+        if (const int rc = ivf_read_bad(v, &bad); rc != FX_OK) return rc;
+        if (bad > 0) return ivf_bad_error(bad, v->nlist);
+    }
+    return FX_OK;
+}
+
+int fx_ivf_search(FxIvf* v, int64_t nq, const void* q, int q_dtype, int q_mem, int k, int nprobe, float* D, int64_t* I,
+                  int out_mem) {
+    if (nq < 0) return set_err(FX_E_ARG, "negative nq");
+    if (k < 1) return set_err(FX_E_ARG, "k must be positive (got %d)", k);
+    if (nprobe < 1) return set_err(FX_E_ARG, "nprobe must be positive (got %d)", nprobe);
+    if (!check_dtype(q_dtype)) return set_err(FX_E_ARG, "bad query dtype %d", q_dtype);
+    if (!valid_mem(q_mem) || !valid_mem(out_mem)) return set_err(FX_E_ARG, "bad q_mem / out_mem");
+    if (k > FX_MAX_K) return set_err(FX_E_UNSUPPORTED, "ivf search: k = %d above FX_MAX_K = %d", k, FX_MAX_K);
+    if (!v) return set_err(FX_E_ARG, "null ivf index");
+    std::lock_guard<std::mutex> lk(v->mu);
+    if (const int rc = ivf_trained(v, "ivf search"); rc != FX_OK) return rc;
+    if (nq == 0) return FX_OK;
+    if (!q || !D || !I) return set_err(FX_E_ARG, "null buffer");
+    const int np = (int)std::min<int64_t>(nprobe, v->nlist);
+    if (nq * np >= (int64_t)INT32_MAX)
+        return set_err(FX_E_UNSUPPORTED, "ivf search: nq * nprobe = %lld pairs (limit 2^31-1)", (long long)(nq * np));
+    if (np > FX_MAX_K)
+        return set_err(FX_E_UNSUPPORTED, "ivf search: nprobe = %d above %d (the coarse search's k)", np, FX_MAX_K);
+    FxIndex* p = v->pay;
+    DeviceGuard g(p->device);
+    if (!g.ok) return set_err(FX_E_HIP, "hipSetDevice(%d) failed", p->device);
+    if (const int rc = ivf_regroup(v); rc != FX_OK) return rc;
+    // (an earlier device search's counts, if nobody asked for them, give way to this search's)
+    v->counts_pending = false;
+    v->last_fallbacks = v->last_dropped = v->last_bad_probe = 0;
+    if (p->ntotal == 0) return fill_missing(p, nq, k, D, I, out_mem);
+
+    hipStream_t s = p->stream();
+    const IvfPlan P = plan_ivf(nq, np, v->nlist, v->max_list_rows, p->ntotal, k, p->row_bytes);
+    v->last_plan[0] = P.path;
+    v->last_plan[1] = P.chunks;
+    v->last_plan[2] = P.slots;
+    v->last_qbatch = P.q_batch;
+    v->last_grid = P.grid;
+    const int qes = dtype_size(q_dtype);
+    const void* qdev = nullptr;
+    HIP_TRY(stage_in(p, v->qin, q, (size_t)nq * p->d * qes, q_mem, &qdev));
+    const bool host_out = out_mem == FX_MEM_HOST;
+    float* Dd = D;
+    int64_t* Id = I;
+    if (host_out) {
+        HIP_TRY(v->outD.ensure((size_t)nq * k * 4));
+        HIP_TRY(v->outI.ensure((size_t)nq * k * 8));
+        Dd = (float*)v->outD.p;
+        Id = (int64_t*)v->outI.p;
+    }
+    HIP_TRY(hipMemsetAsync(v->cnt, 0, 16, s));
+    const int C = P.chunks, slots = P.slots;
+    const bool fused = P.path == IVF_PATH_FUSED;
+    const int64_t qb_max = std::min(P.q_batch, nq);
+    const int64_t nq_pad_max = round_up(qb_max, QPAD);
+    HIP_TRY(v->coarse_d.ensure((size_t)qb_max * np * 4));
+    HIP_TRY(v->coarse_i.ensure((size_t)qb_max * np * 8));
+    HIP_TRY(v->flag.ensure((size_t)(qb_max + 1) * 4));
+    HIP_TRY(v->qb.f32.ensure((size_t)nq_pad_max * p->kdim * 4));
+    const size_t ncand = (size_t)qb_max * slots * (fused ? KP : k);
+    HIP_TRY(v->cand_d.ensure(ncand * 4));
+    HIP_TRY(v->cand_i.ensure(ncand * 4));
+    if (fused) {
+        HIP_TRY(v->qb.op.ensure((size_t)nq_pad_max * p->row_bytes));
+        HIP_TRY(v->qb.eps.ensure((size_t)qb_max * 4));
+        HIP_TRY(v->qb.rho.ensure((size_t)qb_max * 4));
+        HIP_TRY(v->qb.shift.ensure((size_t)qb_max * 8));
+        HIP_TRY(v->pkeys.ensure((size_t)qb_max * np * 8));
+        HIP_TRY(v->psorted.ensure((size_t)qb_max * np * 8));
+        HIP_TRY(v->seg.ensure((size_t)(v->nlist + 1) * 4));
+        HIP_TRY(v->ngrp.ensure((size_t)(v->nlist + 1) * 4));
+        HIP_TRY(v->gbase.ensure((size_t)(v->nlist + 1) * 4));
+        // hipCUB's temporaries for every pass size that occurs: full passes and a shorter last one
+        size_t tb = 0, tb_last = 0;
+        HIP_TRY(ivf_pairs_temp_bytes(qb_max * np, v->nlist, &tb));
+        if (nq % qb_max != 0) HIP_TRY(ivf_pairs_temp_bytes((nq % qb_max) * np, v->nlist, &tb_last));
+        HIP_TRY(v->ptemp.ensure(std::max<size_t>(std::max(tb, tb_last), 16)));
+    }
+    int* n_flag = (int*)v->flag.p;
+
+    for (int64_t q0 = 0; q0 < nq; q0 += qb_max) {
+        const int64_t qb = std::min(qb_max, nq - q0);
+        const void* qp = (const char*)qdev + (size_t)q0 * p->d * qes;
+        hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (v->profile) {
+            for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+            v->ev.insert(v->ev.end(), ev, ev + 5);
+            HIP_TRY(hipEventRecord(ev[0], s));
+        }
+        // 1. coarse: the quantizer's exact top-np search names the probed lists
+        {
+            BorrowQuant bq(v->quant, s);
+            HIP_TRY(bq.begin());
+            const int rc = do_search(v->quant, qb, qp, q_dtype, FX_MEM_DEVICE, np, (float*)v->coarse_d.p,
+                                     (int64_t*)v->coarse_i.p, FX_MEM_DEVICE);
+            if (rc != FX_OK) return rc;
+        }
+        if (v->profile) HIP_TRY(hipEventRecord(ev[1], s));
+        IvfExact ex{};
+        ex.codes = p->codes;
+        ex.row_bytes = p->row_bytes;
+        ex.kdim = p->kdim;
+        ex.list_off = v->list_off;
+        ex.nlist = v->nlist;
+        ex.coarse = (const int64_t*)v->coarse_i.p;
+        ex.np = np;
+        ex.C = C;
+        ex.qf32 = (const float*)v->qb.f32.p;
+        ex.n_flag = n_flag;
+        ex.k = k;
+        ex.cd = (float*)v->cand_d.p;
+        ex.ci = (int*)v->cand_i.p;
+        ex.labels = p->idm.labels;
+        ex.D = Dd + q0 * k;
+        ex.I = Id + q0 * k;
+        if (!fused) {
+            // the exact path for the whole pass: every query "flagged"
+            HIP_TRY(launch_f32_queries(qp, q_dtype, qb, p->d, p->kdim, (float*)v->qb.f32.p, s));
+            HIP_TRY(launch_ivf_count_bad(ex.coarse, qb * np, v->nlist, v->cnt + 2, s));
+            HIP_TRY(launch_ivf_flag_all(n_flag, qb, s));
+            if (v->profile) HIP_TRY(hipEventRecord(ev[2], s));
+            HIP_TRY(launch_ivf_exact(p->dtype, p->metric, ex, s));
+            if (v->profile) {  // (the exact scan is this path's "list scan"; it has no refine)
+                HIP_TRY(hipEventRecord(ev[3], s));
+                HIP_TRY(hipEventRecord(ev[4], s));
+            }
+            continue;
+        }
+        // 2. the pass's (query, list) pairs grouped by list
+        IvfPairs pr{};
+        pr.coarse = ex.coarse;
+        pr.npairs = qb * np;
+        pr.nlist = v->nlist;
+        pr.list_off = v->list_off;
+        pr.keys = (uint64_t*)v->pkeys.p;
+        pr.sorted = (uint64_t*)v->psorted.p;
+        pr.seg = (int*)v->seg.p;
+        pr.ngrp = (int*)v->ngrp.p;
+        pr.gbase = (int*)v->gbase.p;
+        pr.bad = v->cnt + 2;
+        HIP_TRY(launch_ivf_pairs(pr, v->ptemp.p, v->ptemp.bytes, s));
+        // query operands over the stored rows with plain norms (no image), as range_search prepares them
+        const int64_t nq_pad = round_up(qb, QPAD);
+        PrepParams pp{};
+        base_prep(p, v->qb, qp, q_dtype, qb, nq_pad, p->dtype, pp);
+        pp.zero[1] = n_flag;
+        HIP_TRY(launch_prep_queries(pp, s));
+        // 3. the list scan; slots no block writes hold id -1
+        HIP_TRY(hipMemsetAsync(v->cand_i.p, 0xff, (size_t)qb * slots * KP * 4, s));
+        IvfScan sc{};
+        sc.codes = p->codes;
+        sc.norms = p->norms;
+        sc.row_bytes = p->row_bytes;
+        sc.list_off = v->list_off;
+        sc.nlist = v->nlist;
+        sc.qop = (const char*)v->qb.op.p;
+        sc.np = np;
+        sc.C = C;
+        sc.sorted = pr.sorted;
+        sc.seg = pr.seg;
+        sc.gbase = pr.gbase;
+        sc.cand_d = (float*)v->cand_d.p;
+        sc.cand_i = (int*)v->cand_i.p;
+        sc.grid = (qb * np / TILE_Q + std::min<int64_t>(v->nlist, qb * np)) * C;
+        if (v->profile) HIP_TRY(hipEventRecord(ev[2], s));
+        HIP_TRY(launch_ivf_scan(p->dtype, p->metric, sc, s));
+        if (v->profile) HIP_TRY(hipEventRecord(ev[3], s));
+        // 4. refine + certification over the query's slots (one "query tile" per query)
+        RefineParams rp{};
+        rp.cand_d = sc.cand_d;
+        rp.cand_i = sc.cand_i;
+        rp.splits = slots;
+        rp.qt = 1;
+        rp.nq = qb;
+        rp.ntotal = p->ntotal;
+        rp.k = k;
+        rp.codes = p->codes;
+        rp.row_bytes = p->row_bytes;
+        rp.kdim = p->kdim;
+        rp.qf32 = pp.qf32;
+        rp.qeps = pp.qeps;
+        rp.qrho = pp.qrho;
+        rp.qshift = pp.qshift;
+        rp.id_offset = 0;
+        rp.labels = p->idm.labels;
+        rp.D = ex.D;
+        rp.I = ex.I;
+        rp.n_flag = n_flag;
+        rp.flag_list = n_flag + 1;
+        rp.n_drop = v->cnt;
+        rp.prefetch = qb <= 256 ? 4 : 1;
+        rp.k1 = 0;
+        rp.force_fb = v->quant->opt.force_fallback != 0;  // (the diagnostic build's hook, set on the quantizer)
+        rp.gtau = nullptr;
+        rp.wg = 0;
+        HIP_TRY(launch_refine(p->dtype, p->metric, rp, s));
+        // 5. the flagged queries' exact lists (device-gated; the candidate buffers are free again)
+        HIP_TRY(launch_ivf_exact(p->dtype, p->metric, ex, s));
+        HIP_TRY(launch_ivf_accum(v->cnt + 1, n_flag, s));
+        if (v->profile) HIP_TRY(hipEventRecord(ev[4], s));
+    }
+    HIP_TRY(hipMemcpyAsync(v->pin_cnt, v->cnt, 12, hipMemcpyDeviceToHost, s));
+    v->counts_pending = true;
+    if (!host_out) return FX_OK;
+    HIP_TRY(hipMemcpyAsync(D, Dd, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(I, Id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
+    if (const int rc = ivf_read_counts(v); rc != FX_OK) return rc;
+    return v->last_dropped > 0 || v->last_bad_probe > 0 ? ivf_integrity(v) : FX_OK;
+}
+
+int fx_ivf_reset(FxIvf* v) {
+    if (!v) return set_err(FX_E_ARG, "null ivf index");
+    std::lock_guard<std::mutex> lk(v->mu);
+    if (const int rc = fx_index_reset(v->pay); rc != FX_OK) return rc;
+    DeviceGuard g(v->pay->device);
+    HIP_TRY(hipMemset(v->list_off, 0, (size_t)(v->nlist + 1) * 4));
+    HIP_TRY(hipMemset(v->bad, 0, 8));
+    v->h_off.assign((size_t)v->nlist + 1, 0);
+    v->max_list_rows = 0;
+    v->dirty = false;
+    v->sequential = false;
+    return FX_OK;
+}
+
+int fx_ivf_ntotal(const FxIvf* v, int64_t* out) {
+    if (!v || !out) return set_err(FX_E_ARG, "null argument");
+    *out = v->pay->ntotal;
+    return FX_OK;
+}
+
+int fx_ivf_list_sizes(FxIvf* v, int64_t* out) {
+    if (!v || !out) return set_err(FX_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(v->mu);
+    DeviceGuard g(v->pay->device);
+    if (const int rc = ivf_regroup(v); rc != FX_OK) return rc;
+    for (int64_t l = 0; l < v->nlist; ++l) out[l] = (int64_t)v->h_off[l + 1] - v->h_off[l];
+    return FX_OK;
+}
+
+int fx_ivf_list_ids(FxIvf* v, int64_t list, int64_t* out, int64_t cap, int64_t* n) {
+    if (!v || !n) return set_err(FX_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(v->mu);
+    if (list < 0 || list >= v->nlist)
+        return set_err(FX_E_ARG, "ivf list_ids: list %lld outside [0, %lld)", (long long)list, (long long)v->nlist);
+    DeviceGuard g(v->pay->device);
+    if (const int rc = ivf_regroup(v); rc != FX_OK) return rc;
+    const int64_t r0 = v->h_off[list], cnt = (int64_t)v->h_off[list + 1] - r0;
+    *n = cnt;
+    if (cnt == 0 || cap <= 0) return FX_OK;
+    if (!out) return set_err(FX_E_ARG, "null buffer");
+    hipStream_t s = v->pay->stream();
+    HIP_TRY(hipMemcpyAsync(out, v->pay->idm.labels + r0, (size_t)std::min(cnt, cap) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return FX_OK;
+}
+
+int fx_ivf_set_stream(FxIvf* v, void* stream) {
+    if (!v) return set_err(FX_E_ARG, "null ivf index");
+    std::lock_guard<std::mutex> lk(v->mu);
+    return fx_index_set_stream(v->pay, stream);
+}
+
+int fx_ivf_last_counts(FxIvf* v, int64_t* fallbacks, int64_t* exact_fallbacks, int64_t* dropped) {
+    if (!v || !fallbacks || !exact_fallbacks || !dropped) return set_err(FX_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(v->mu);
+    if (const int rc = ivf_read_counts(v); rc != FX_OK) return rc;
+    // (a flagged query goes straight to the exact list scan: both counts are the same)
+    *fallbacks = v->last_fallbacks;
+    *exact_fallbacks = v->last_fallbacks;
+    *dropped = v->last_dropped + v->last_bad_probe;
+    return FX_OK;
+}
+
+int fx_ivf_profile(FxIvf* v, int enable) {
+    if (!v) return set_err(FX_E_ARG, "null ivf index");
+    std::lock_guard<std::mutex> lk(v->mu);
+    v->profile = enable != 0;
+    return FX_OK;
+}
+
+int fx_ivf_profile_read(FxIvf* v, double* coarse_ms, double* pairs_ms, double* scan_ms, double* refine_ms,
+                        int64_t* passes) {
+    if (!v || !coarse_ms || !pairs_ms || !scan_ms || !refine_ms || !passes) return set_err(FX_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(v->mu);
+    DeviceGuard g(v->pay->device);
+    HIP_TRY(hipStreamSynchronize(v->pay->stream()));
+    double ms[4] = {0, 0, 0, 0};
+    float t = 0;
+    for (size_t i = 0; i + 4 < v->ev.size(); i += 5)
+        for (int part = 0; part < 4; ++part) {
+            HIP_TRY(hipEventElapsedTime(&t, v->ev[i + part], v->ev[i + part + 1]));
+            ms[part] += t;
+        }
+    *passes = (int64_t)(v->ev.size() / 5);
+    for (hipEvent_t e : v->ev) (void)hipEventDestroy(e);
+    v->ev.clear();
+    *coarse_ms = ms[0];
+    *pairs_ms = ms[1];
+    *scan_ms = ms[2];
+    *refine_ms = ms[3];
+    return FX_OK;
+}
+
+int fx_ivf_last_plan(FxIvf* v, int* path, int* chunks, int* slots, int64_t* q_batch, int64_t* grid) {
+    if (!v || !path || !chunks || !slots || !q_batch || !grid) return set_err(FX_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(v->mu);
+    *path = v->last_plan[0];
+    *chunks = v->last_plan[1];
+    *slots = v->last_plan[2];
+    *q_batch = v->last_qbatch;
+    *grid = v->last_grid;
+    return FX_OK;
+}
+
+}  // extern "C"

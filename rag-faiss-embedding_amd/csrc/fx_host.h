@@ -520,6 +520,43 @@ struct FxIndex {
     fx::IndexShape shape() const { return {ntotal, row_bytes, dtype, metric, img_kind}; }
 };
 
+// ---- fx_api_ivf.cpp ------------------------------------------------------------
+
+// An inverted-file index (include/fx_index.h, fx_ivf.hip).  `quant` is the
+// caller's coarse quantizer (borrowed); `pay` the payload it owns: a labelled
+// flat index whose rows are in list order once `dirty` is false.  row_list[r] is
+// the list of payload row r (nlist: an assignment outside the lists).
+struct FxIvf {
+    FxIndex* quant = nullptr;
+    FxIndex* pay = nullptr;
+    int64_t nlist = 0;
+    bool dirty = false;         // rows were appended since the last regroup
+    bool sequential = false;    // ids are ntotal .. (fx_ivf_add without ids); decided by the first add
+    int64_t max_list_rows = 0;  // of the last regroup
+    std::vector<int> h_off;     // list_off on the host, read back with it ([nlist + 1])
+    fx::DevArr<int> row_list, row_list_alt, list_off, max_rows;
+    fx::DevArr<char> codes_alt;
+    fx::DevArr<float> norms_alt;
+    fx::DevArr<int64_t> labels_alt;
+    fx::DevBuf rws;             // the regroup's sort workspace
+    fx::DevBuf assign, ids;     // a chunk's k = 1 search results; sequential ids of an add
+    fx::DevArr<unsigned long long> bad;  // assignments outside [0, nlist) since the last read
+    // search workspace
+    fx::QueryBufs qb;
+    fx::DevBuf qin, coarse_d, coarse_i, pkeys, psorted, seg, ngrp, gbase, ptemp, cand_d, cand_i, flag, outD, outI;
+    fx::DevArr<int> cnt;        // [0] dropped candidate ids, [1] queries flagged, [2] coarse entries outside the lists
+    fx::PinArr<int> pin_cnt;
+    bool counts_pending = false;
+    int64_t last_fallbacks = 0, last_dropped = 0, last_bad_probe = 0;
+    int last_plan[3] = {0, 0, 0};  // path, chunks, slots
+    int64_t last_qbatch = 0, last_grid = 0;
+    // profiling (fx_ivf_profile): 5 events per pass -- start, after the coarse search, after pairs + query
+    // preparation, after the list scan, after refine + exact fallback
+    bool profile = false;
+    std::vector<hipEvent_t> ev;
+    std::mutex mu;
+};
+
 // A selector (include/fx_index.h): the device image fx_select.hip builds of a
 // subset of `index`'s rows [0, ntotal) as they were at creation.
 struct FxSelector {

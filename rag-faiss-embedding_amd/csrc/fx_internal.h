@@ -1,5 +1,5 @@
 // fx_internal.h -- shared between the HIP translation units (fx_kernels.hip,
-// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip, fx_kmeans.hip) and the host C ABI
+// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip, fx_kmeans.hip, fx_ivf.hip) and the host C ABI
 // (fx_index.cpp, fx_api_*.cpp, fx_plan.cpp; their own header: fx_host.h):
 // tiling constants, kernel parameter blocks, the launchers' prototypes and
 // their host-side helpers.  Not part of the public ABI (include/fx_index.h).
@@ -449,6 +449,100 @@ struct KmFinish {
     int64_t* n_split;       // out: empty clusters repaired
 };
 hipError_t launch_km_finish(const KmFinish& f, hipStream_t s);
+// inverted file (fx_ivf.hip): IndexIVFFlat over a list-ordered payload.
+// Regroup: rows [0, n) of (codes, norms, labels, row_list) -> the same rows in
+// list order (stable: insertion order within a list) in the dst arrays;
+// list_off[l] = first row of list l (list_off[nlist] = rows with a valid list),
+// *max_rows = the longest list.  A row_list entry outside [0, nlist) sorts last,
+// past list_off[nlist].  ws: ivf_regroup_bytes(n, nlist).
+struct IvfRegroup {
+    int64_t n, nlist;  // n <= 2^31-1
+    int row_bytes;
+    const char* codes;
+    const float* norms;
+    const int64_t* labels;
+    const int* row_list;
+    char* dst_codes;
+    float* dst_norms;
+    int64_t* dst_labels;
+    int* dst_row_list;
+    int* list_off;  // [nlist + 1]
+    int* max_rows;  // one word
+};
+hipError_t ivf_regroup_bytes(int64_t n, int64_t nlist, size_t* bytes);
+hipError_t launch_ivf_regroup(const IvfRegroup& r, void* ws, size_t ws_bytes, hipStream_t s);
+// row_list[i] = (int)assign[i] for i < n; an assignment outside [0, nlist) is stored as nlist and counted in *bad
+hipError_t launch_ivf_record(const int64_t* assign, int64_t n, int64_t nlist, int* row_list, unsigned long long* bad,
+                             hipStream_t s);
+// ids[i] = first + i
+hipError_t launch_ivf_iota(int64_t* ids, int64_t n, int64_t first, hipStream_t s);
+// The (query, probed list) pairs of a pass, grouped by list on the device:
+// pair p = q * np + j probes list coarse[p]; sorted = the pairs as list << 32 |
+// p ordered by list (stable); seg[l] = first sorted position of list l, gbase =
+// exclusive scan of ceil(count_l / TILE_Q) over the NON-EMPTY lists (a list
+// without rows forms no group), so gbase[nlist] is the pass's group total.  A
+// coarse entry outside [0, nlist) forms no pair and is counted in *bad.
+struct IvfPairs {
+    const int64_t* coarse;  // [npairs]
+    int64_t npairs;         // <= 2^31-1
+    int64_t nlist;
+    const int* list_off;    // [nlist + 1]
+    uint64_t* keys;         // [npairs] scratch
+    uint64_t* sorted;       // [npairs]
+    int* seg;               // [nlist + 1]
+    int* ngrp;              // [nlist + 1] scratch
+    int* gbase;             // [nlist + 1]
+    int* bad;               // one counter (added to)
+};
+hipError_t ivf_pairs_temp_bytes(int64_t npairs, int64_t nlist, size_t* bytes);
+hipError_t launch_ivf_pairs(const IvfPairs& p, void* temp, size_t temp_bytes, hipStream_t s);
+// k_ivf_scan: one workgroup per (query group, chunk): the MFMA tile loop over
+// the chunk's tiles of the group's list against the group's <= TILE_Q queries,
+// fetched through the sorted pairs; the sorted top-KP of (item, query) ->
+// cand[q][j * C + chunk][KP].  cand_i must hold -1 wherever no block writes.
+struct IvfScan {
+    const char* codes;    // the payload in list order
+    const float* norms;
+    int row_bytes;
+    const int* list_off;
+    int64_t nlist;
+    const char* qop;      // [nq_pad][row_bytes] prepared query operands of the pass
+    int np, C;            // probes per query, chunks per list
+    const uint64_t* sorted;
+    const int* seg;
+    const int* gbase;
+    float* cand_d;        // [nq][np * C][KP]
+    int* cand_i;
+    int64_t grid;
+};
+hipError_t launch_ivf_scan(int st_dt, int metric, const IvfScan& p, hipStream_t s);
+// k_ivf_exact + k_ivf_merge: the exact fp64 ranking of the probed lists' rows
+// for the queries n_flag[1 ..] (count n_flag[0], read on the device: nothing
+// runs when it is 0).  Item (flagged f, probe j, chunk c) -> cd / ci[item][k];
+// the merge ranks a query's np * C lists under (key, row) -> D / I.
+struct IvfExact {
+    const char* codes;
+    int row_bytes, kdim;
+    const int* list_off;
+    int64_t nlist;
+    const int64_t* coarse;  // [nq][np]
+    int np, C;
+    const float* qf32;      // [nq][kdim]
+    const int* n_flag;
+    int k;
+    float* cd;              // [flagged * np * C][k]
+    int* ci;
+    const int64_t* labels;
+    float* D;               // [nq][k]
+    int64_t* I;
+};
+hipError_t launch_ivf_exact(int st_dt, int metric, const IvfExact& p, hipStream_t s);
+// *bad += the entries of coarse[0, n) outside [0, nlist) (the exact path of a whole pass, which forms no pairs)
+hipError_t launch_ivf_count_bad(const int64_t* coarse, int64_t n, int64_t nlist, int* bad, hipStream_t s);
+// flag[0] = n, flag[1 + i] = i (the exact path of a whole pass)
+hipError_t launch_ivf_flag_all(int* flag, int64_t n, hipStream_t s);
+// *total += *n_flag
+hipError_t launch_ivf_accum(int* total, const int* n_flag, hipStream_t s);
 // queries [n][d] (dtype q_dt, on the device) -> fp32 [n][kdim], zero padded (fx_hugek.hip: k_hk_queries)
 hipError_t launch_f32_queries(const void* q, int q_dt, int64_t n, int d, int kdim, float* out, hipStream_t s);
 // bits[0] <- max(bits[0], float bits of the largest of norms[0, n)) (atomicMax)

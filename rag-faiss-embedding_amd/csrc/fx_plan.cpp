@@ -181,6 +181,35 @@ HostOut host_out_layout(int64_t nq, int k) {
     return L;
 }
 
+IvfPlan plan_ivf(int64_t nq, int nprobe_eff, int64_t nlist, int64_t max_list_rows, int64_t ntotal, int k,
+                 int row_bytes) {
+    // ntotal and row_bytes are part of the planner's signature but do not enter today: the chunk count
+    // follows the longest list's tiles, whatever a tile costs.  `tiles` below is the planner's upper
+    // bound on a list's tiles (tiles_per_chunk: for checks); k_ivf_scan divides each list's own tile
+    // count by C, so only C, slots, q_batch and grid reach the launch.
+    (void)ntotal;
+    (void)row_bytes;
+    IvfPlan P;
+    P.path = k <= KP ? IVF_PATH_FUSED : IVF_PATH_EXACT;
+    const int64_t np = std::max(1, nprobe_eff);
+    const int64_t tiles = (std::max<int64_t>(max_list_rows, 0) + TILE_R - 1) / TILE_R + 1;
+    const int64_t pairs = std::max<int64_t>(nq, 1) * np;
+    int64_t C = 1;
+    if (pairs < 256) {
+        C = (512 + pairs - 1) / pairs;
+        C = std::min<int64_t>(C, std::max<int64_t>(1, tiles / 4));
+        C = std::min<int64_t>(C, 64);
+    }
+    P.chunks = (int)C;
+    P.tiles_per_chunk = (int)((tiles + C - 1) / C);
+    P.slots = (int)(np * C);
+    const int64_t per_query = (int64_t)P.slots * (P.path == IVF_PATH_FUSED ? KP : k) * 8;
+    P.q_batch = std::max<int64_t>(1, std::min<int64_t>(std::max<int64_t>(nq, 1), IVF_CAND_BYTES / per_query));
+    const int64_t bp = P.q_batch * np;
+    P.grid = (bp / TILE_Q + std::min<int64_t>(nlist, bp)) * C;
+    return P;
+}
+
 bool plan_remove(const KeptPrefix& P, int64_t stage_rows, std::vector<RemoveChunk>& out) {
     const int64_t g = P.g, nt = P.ntotal;
     const int64_t nb = (nt + g - 1) / g;  // boundary i is row min(nt, i g)

@@ -50,6 +50,33 @@ struct HostOut {
 };
 HostOut host_out_layout(int64_t nq, int k);
 
+// ---- inverted file (fx_ivf.hip): the plan of one IndexIVFFlat search ---------
+
+// path: the fused MFMA list scan + refine (k <= KP), or the exact list scan
+// (k_ivf_exact) for the whole search.
+enum { IVF_PATH_FUSED = 0, IVF_PATH_EXACT = 1 };
+struct IvfPlan {
+    int path = IVF_PATH_FUSED;
+    int chunks = 1;           // C: tile chunks per probed list
+    int tiles_per_chunk = 1;  // ceil(tiles of the longest list / C): an upper bound for checks only -- the
+                              // kernel divides each list's own tiles by C itself
+    int slots = 1;            // candidate lists per query: nprobe_eff * C
+    int64_t q_batch = 1;      // queries per pass
+    int64_t grid = 0;         // upper bound of the list scan's workgroups in a pass
+};
+// candidate bytes a pass may hold (entries of 8 B: key + row)
+constexpr int64_t IVF_CAND_BYTES = 1ll << 30;
+// A list of r rows whose start is aligned down to 4 rows touches up to
+// ceil(r / 128) + 1 tiles.  C > 1 only when a pass has fewer than 256 (query,
+// list) pairs: then the pairs alone cannot fill the CUs, and each list is cut
+// into chunks of >= 4 tiles until ~512 workgroups exist (at most 64 chunks).
+// q_batch: the most queries whose candidate lists (slots * KP entries each;
+// exact path: slots * k) fit IVF_CAND_BYTES.  grid: a pass of P = q_batch *
+// nprobe_eff pairs forms sum_l ceil(c_l / 128) <= P / 128 + min(nlist, P) query
+// groups, each scanned by C workgroups.
+IvfPlan plan_ivf(int64_t nq, int nprobe_eff, int64_t nlist, int64_t max_list_rows, int64_t ntotal, int k,
+                 int row_bytes);
+
 // ---- remove_ids (fx_remove.hip): the host's chunk plan ----------------------
 
 // Kept rows before row r, for the rows the plan asks about: any row (the

@@ -1080,9 +1080,287 @@ class Kmeans:
         return D.reshape(-1).cpu().numpy(), I.reshape(-1).cpu().numpy()
 
 
+# ---------------------------------------------------------------------------
+# faiss.IndexIVFFlat (include/fx_index.h "inverted file")
+# ---------------------------------------------------------------------------
+class SearchParametersIVF(SearchParameters):
+    """``faiss.SearchParametersIVF(nprobe=1)``: per-search parameters of an
+    ``IndexIVFFlat``.  A selector (``sel``) is accepted here as in faiss but
+    the IVF search does not take one (``NotImplementedError``)."""
+
+    def __init__(self, sel: Optional[IDSelector] = None, nprobe: int = 1):
+        super().__init__(sel)
+        self.nprobe = int(nprobe)
+
+
+class IndexIVFFlat:
+    """``faiss.IndexIVFFlat(quantizer, d, nlist, metric)``: rows live in
+    ``nlist`` inverted lists, row i in list ``quantizer.search(x_i, 1)``; a
+    search ranks only the rows of the ``nprobe`` lists ``quantizer.search(q,
+    nprobe)`` names.  Within those lists the result is exact as the flat
+    index's is (ids bit-exact, distances the fp64 sum rounded once), ranked by
+    (distance, list number, insertion order within the list); with ``nprobe =
+    nlist`` it reproduces the flat index.
+
+    ``quantizer`` is an unlabelled ``IndexFlatL2`` / ``IndexFlatIP`` of this
+    module on the same device; this object keeps it alive.  ``is_trained`` is
+    True as soon as ``quantizer.ntotal == nlist``, so centroids saved with
+    ``write_index(quantizer)`` and read back make a trained index.
+
+    ``train(x)`` on an untrained index runs this module's ``Kmeans(d, nlist,
+    niter, seed, max_points_per_centroid=256)`` -- L2 Lloyd iterations, which
+    is what faiss does for the level-1 quantizer as remembered; it is not
+    checked against a faiss build -- and adds the centroids to the quantizer.
+
+    Not offered: ``write_index`` / ``read_index`` of the IVF index itself
+    (persist the quantizer and re-add), ``remove_ids``, ``range_search``,
+    selectors, ``reconstruct*``, ``search_preassigned``."""
+
+    def __init__(self, quantizer, d: int, nlist: int, metric: int = METRIC_L2, dtype: str = "float32",
+                 device: int = 0, niter: int = 10, seed: int = 1234):
+        if dtype not in _DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(_DTYPES)}")
+        assert isinstance(quantizer, _FlatIndex), "quantizer must be an IndexFlatL2 / IndexFlatIP of this module"
+        assert quantizer.d == int(d), f"quantizer has d = {quantizer.d}, the index d = {int(d)}"
+        assert quantizer.device == int(device), f"quantizer on cuda:{quantizer.device}, index on cuda:{int(device)}"
+        assert metric in (METRIC_L2, METRIC_INNER_PRODUCT), "metric must be METRIC_L2 or METRIC_INNER_PRODUCT"
+        self.quantizer = quantizer
+        self._lib = quantizer._lib
+        self._d, self.nlist, self.metric_type = int(d), int(nlist), int(metric)
+        self.storage_dtype, self.device = dtype, int(device)
+        self.nprobe = 1
+        self.niter, self.seed = int(niter), int(seed)
+        self.verbose = False
+        self._mode = None  # "seq" (add) or "ids" (add_with_ids) while the index holds rows
+        self._h = ctypes.c_void_p()
+        self._check(self._lib.fx_ivf_create(quantizer._h, self._d, self.nlist, _DTYPES[dtype], self.metric_type,
+                                            ctypes.byref(self._h)))
+
+    def _check(self, rc: int) -> None:
+        check(rc, self._lib)
+
+    @property
+    def d(self) -> int:
+        return self._d
+
+    @property
+    def ntotal(self) -> int:
+        v = ctypes.c_int64(0)
+        self._check(self._lib.fx_ivf_ntotal(self._h, ctypes.byref(v)))
+        return v.value
+
+    @property
+    def is_trained(self) -> bool:
+        return self.quantizer.ntotal == self.nlist
+
+    def _bind_stream(self, use_torch: bool) -> None:
+        s = _torch().cuda.current_stream(self.device).cuda_stream if use_torch else None
+        if getattr(self, "_bound", _UNBOUND) == s:
+            return
+        self._check(self._lib.fx_ivf_set_stream(self._h, ctypes.c_void_p(s) if s is not None else None))
+        self._bound = s
+
+    def train(self, x) -> None:
+        """Train the coarse quantizer (a no-op on a trained index, as faiss)."""
+        if self.is_trained:
+            return
+        assert self.quantizer.ntotal == 0, "the quantizer holds rows but not nlist of them"
+        km = Kmeans(self._d, self.nlist, niter=self.niter, seed=self.seed, max_points_per_centroid=256,
+                    dtype=self.quantizer.storage_dtype, device=self.device)
+        km.train(x)
+        self.quantizer.add(km.centroids)
+
+    def _add(self, x, ids) -> None:
+        assert self.is_trained, "the index is not trained"
+        mode = "seq" if ids is None else "ids"
+        if self.ntotal > 0 and self._mode is not None and mode != self._mode:
+            raise AssertionError("add does not make sense on an index with labels: use add_with_ids" if mode == "seq"
+                                 else "add_with_ids not implemented for an index that holds rows without labels")
+        iptr, imem, dev_ids, n_ids = None, _lib.MEM_HOST, False, None
+        if ids is not None:
+            dev_ids = _is_device_tensor(ids)
+            ids = _id_array(ids)
+            n_ids = int(ids.numel()) if dev_ids else int(ids.size)
+            if dev_ids:
+                assert ids.device.index == self.device, f"ids on cuda:{ids.device.index}, index on cuda:{self.device}"
+                iptr, imem = ctypes.c_void_p(ids.data_ptr()), _lib.MEM_DEVICE
+            else:
+                iptr = ctypes.c_void_p(ids.ctypes.data)
+        if _is_device_tensor(x):
+            assert x.dim() == 2 and x.shape[1] == self._d, "dimension mismatch"
+            assert x.device.index == self.device, f"tensor on cuda:{x.device.index}, index on cuda:{self.device}"
+            x = x.contiguous()
+            xptr, code, mem, n = ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x), _lib.MEM_DEVICE, x.shape[0]
+            self._bind_stream(True)
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+            assert x.ndim == 2 and x.shape[1] == self._d, "dimension mismatch"
+            xptr, code, mem, n = x.ctypes.data_as(ctypes.c_void_p), _lib.F32, _lib.MEM_HOST, x.shape[0]
+            self._bind_stream(dev_ids)
+        assert n_ids is None or n_ids == n, f"add_with_ids: {n_ids} ids for {n} rows"
+        self._check(self._lib.fx_ivf_add(self._h, n, xptr, code, mem, iptr, imem))
+        if n > 0:
+            self._mode = mode
+
+    def add(self, x) -> None:
+        """Append the rows of ``x`` with ids ``ntotal .. ntotal + n - 1``."""
+        self._add(x, None)
+
+    def add_with_ids(self, x, ids) -> None:
+        """Append the rows of ``x``, row i with id ``ids[i]`` (any int64)."""
+        self._add(x, ids)
+
+    def add_from_index(self, index) -> None:
+        """Append the stored rows of an unlabelled flat index of this module
+        with ids equal to their row numbers there (``add_with_ids``), gathered
+        chunk by chunk in the storage dtype on the device, never through the
+        host."""
+        t = _torch()
+        flat = _flat(index)
+        assert not flat.has_ids and flat.device == self.device and flat.d == self._d
+        n = flat.ntotal
+        for r0 in range(0, n, KMEANS_CHUNK):
+            keys = t.arange(r0, min(n, r0 + KMEANS_CHUNK), dtype=t.int64, device=t.device("cuda", self.device))
+            self.add_with_ids(flat.reconstruct_batch(keys + flat._id_offset, dtype="storage"), keys)
+
+    def _nprobe_of(self, params) -> int:
+        nprobe = self.nprobe
+        if params is not None:
+            if _selector_of(params) is not None:
+                raise NotImplementedError("IndexIVFFlat.search takes no selector")
+            nprobe = getattr(params, "nprobe", nprobe)
+        nprobe = int(nprobe)
+        if nprobe < 1:
+            raise AssertionError("nprobe must be positive")
+        return min(nprobe, self.nlist)
+
+    def search(self, x, k: int, *, params=None, D=None, I=None) -> Tuple:
+        """The k best rows of every query among its ``nprobe`` probed lists
+        (``self.nprobe``, or ``params=SearchParametersIVF(nprobe=...)``; at most
+        ``nlist``).  numpy in -> numpy out (blocks); device tensors in -> device
+        tensors out, stream-ordered (the first search after an add may
+        synchronise once for the regroup).  ``k > MAX_K``: NotImplementedError.
+
+        ``k <= 32`` takes the fused path (MFMA list scan + exact refine), larger
+        k the exact list scan.  Limitation: the refine certifies a query from
+        the room between its k-th and its 32nd candidate, so as k nears 32 more
+        queries fall to the exact list scan (at k = 32 every query whose probed
+        lists hold 32 rows or more): correct, but much slower than small k
+        (``last_fallbacks()`` counts them)."""
+        k = int(k)
+        if k <= 0:
+            raise AssertionError("k must be positive")
+        nprobe = self._nprobe_of(params)
+        assert self.is_trained, "the index is not trained"
+        if k > _lib.MAX_K:
+            raise NotImplementedError(f"IndexIVFFlat.search: k = {k} above MAX_K = {_lib.MAX_K}")
+        if _is_device_tensor(x):
+            t = _torch()
+            assert x.dim() == 2 and x.shape[1] == self._d, "dimension mismatch"
+            assert x.device.index == self.device, f"queries on cuda:{x.device.index}, index on cuda:{self.device}"
+            x = x.contiguous()
+            nq = x.shape[0]
+            if D is None:
+                D = t.empty((nq, k), dtype=t.float32, device=x.device)
+            if I is None:
+                I = t.empty((nq, k), dtype=t.int64, device=x.device)
+            for name, a, dt in (("D", D, t.float32), ("I", I, t.int64)):
+                assert _is_device_tensor(a) and a.device == x.device, f"{name} must be on {x.device}"
+                assert a.dtype == dt and tuple(a.shape) == (nq, k) and a.is_contiguous(), \
+                    f"{name} must be a contiguous {dt} tensor of shape ({nq}, {k})"
+            self._bind_stream(True)
+            self._check(self._lib.fx_ivf_search(self._h, nq, ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x),
+                                                _lib.MEM_DEVICE, k, nprobe, ctypes.c_void_p(D.data_ptr()),
+                                                ctypes.c_void_p(I.data_ptr()), _lib.MEM_DEVICE))
+            return D, I
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        assert x.ndim == 2 and x.shape[1] == self._d, "dimension mismatch"
+        nq = x.shape[0]
+        Dh = np.empty((nq, k), dtype=np.float32) if D is None else D
+        Ih = np.empty((nq, k), dtype=np.int64) if I is None else I
+        for name, a, dt in (("D", Dh, np.float32), ("I", Ih, np.int64)):
+            assert isinstance(a, np.ndarray) and a.dtype == dt and a.shape == (nq, k) and \
+                a.flags.c_contiguous and a.flags.writeable, \
+                f"{name} must be a writeable C-contiguous {np.dtype(dt).name} array of shape ({nq}, {k})"
+        self._bind_stream(False)
+        self._check(self._lib.fx_ivf_search(self._h, nq, x.ctypes.data, _lib.F32, _lib.MEM_HOST, k, nprobe,
+                                            Dh.ctypes.data, Ih.ctypes.data, _lib.MEM_HOST))
+        return Dh, Ih
+
+    def reset(self) -> None:
+        """Empties the lists; the quantizer (the training) stays, as in faiss."""
+        self._check(self._lib.fx_ivf_reset(self._h))
+        self._mode = None
+
+    def list_sizes(self) -> np.ndarray:
+        out = np.zeros(self.nlist, dtype=np.int64)
+        self._check(self._lib.fx_ivf_list_sizes(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def get_list_ids(self, l: int) -> np.ndarray:
+        """The ids of list ``l`` in insertion order (numpy int64)."""
+        n = ctypes.c_int64(0)
+        self._check(self._lib.fx_ivf_list_ids(self._h, int(l), None, 0, ctypes.byref(n)))
+        out = np.empty(n.value, dtype=np.int64)
+        if n.value:
+            self._check(self._lib.fx_ivf_list_ids(self._h, int(l), out.ctypes.data_as(ctypes.c_void_p), n.value,
+                                                  ctypes.byref(n)))
+        return out
+
+    def _counts(self):
+        a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.fx_ivf_last_counts(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+    def last_fallbacks(self) -> int:
+        return self._counts()[0]
+
+    def last_exact_fallbacks(self) -> int:
+        return self._counts()[1]
+
+    def last_dropped_candidates(self) -> int:
+        return self._counts()[2]
+
+    def profile(self, enable: bool = True) -> None:
+        """Record HIP events around the parts of every search pass."""
+        self._check(self._lib.fx_ivf_profile(self._h, 1 if enable else 0))
+
+    def profile_read(self) -> dict:
+        """Milliseconds since the last read (waits for the stream): ``coarse``,
+        ``pairs`` (+ query preparation), ``scan`` (the list scan), ``refine``
+        (+ exact fallback), and the ``passes`` they cover."""
+        ms = [ctypes.c_double(0) for _ in range(4)]
+        n = ctypes.c_int64(0)
+        self._check(self._lib.fx_ivf_profile_read(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(n)))
+        return {"coarse": ms[0].value, "pairs": ms[1].value, "scan": ms[2].value, "refine": ms[3].value,
+                "passes": n.value}
+
+    def last_ivf_plan(self) -> dict:
+        """The planner's outputs for the last search: ``path`` ("fused" /
+        "exact"), ``chunks`` per list, ``slots`` per query, ``q_batch``,
+        ``grid`` (the list scan's launch bound)."""
+        p, c, s = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        qb, g = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.fx_ivf_last_plan(self._h, ctypes.byref(p), ctypes.byref(c), ctypes.byref(s),
+                                               ctypes.byref(qb), ctypes.byref(g)))
+        return {"path": "exact" if p.value else "fused", "chunks": c.value, "slots": s.value, "q_batch": qb.value,
+                "grid": g.value}
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                self._lib.fx_ivf_free(h)
+            except Exception:  # noqa: BLE001 - interpreter shutdown
+                pass
+            self._h = None
+
+
 def write_index(index, path: str) -> None:
     """``faiss.write_index`` (faiss_store.py:91): IxF2 file, fp32 codes; a
     labelled index (``IndexIDMap`` / ``IndexIDMap2``) as an IxM2 file."""
+    if isinstance(index, IndexIVFFlat):
+        raise NotImplementedError("write_index of an IndexIVFFlat: write its quantizer and re-add the rows")
     index = _flat(index)
     check(index._lib.fx_index_write(index._h, str(path).encode()), index._lib)
 

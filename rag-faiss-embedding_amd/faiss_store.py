@@ -32,6 +32,7 @@ class FAISSVectorStore:
 
     _instance = None
     _initialized = False
+    ivf = None  # the IndexIVFFlat over the store's rows (build_ivf); dropped by every call that changes the rows
 
     def __new__(cls, *args, **kwargs):
         if cls._instance is None:
@@ -62,6 +63,7 @@ class FAISSVectorStore:
         """faiss_store.py:36-47.  The ids are recorded before the rows go in,
         and their count is not checked against the rows (as there)."""
         rows = self._as_rows(vectors)
+        self.ivf = None
         self.doc_ids.extend(ids)
         self.index.add(rows)
         logger.info("add: %d ids -> ntotal %d", len(ids), self.index.ntotal)
@@ -74,7 +76,29 @@ class FAISSVectorStore:
         rows = [r for r, doc in enumerate(self.doc_ids) if doc in allowed]
         return _fx.SearchParameters(sel=_fx.IDSelectorBatch(np.asarray(rows, dtype=np.int64)))
 
-    def search(self, query_vector, k: int = 5, allowed_ids=None) -> Tuple[np.ndarray, List[int]]:
+    def build_ivf(self, nlist: int, nprobe: int = 8):
+        """An ``IndexIVFFlat`` over the store's rows (extension): the coarse
+        quantizer is trained on the store's own index, so the rows never leave
+        the GPU, and the rows are added with ids equal to their row numbers, so
+        ``doc_ids`` keeps mapping results.  Kept as ``self.ivf`` until a call
+        changes the rows; ``search(..., nprobe=n)`` uses it.  Errors are logged
+        and raised again, as in ``load_index``."""
+        try:
+            quantizer = _fx.IndexFlatL2(self.dimension, device=self.device)
+            ivf = _fx.IndexIVFFlat(quantizer, self.dimension, int(nlist), _fx.METRIC_L2, dtype=self.dtype,
+                                   device=self.device)
+            ivf.nprobe = int(nprobe)
+            ivf.train(self.index)
+            ivf.add_from_index(self.index)
+            n = self.index.ntotal
+            self.ivf = ivf
+            logger.info("build_ivf: %d rows in %d lists, nprobe %d", n, nlist, nprobe)
+            return ivf
+        except Exception as e:
+            logger.error("build_ivf failed: %s", e)
+            raise
+
+    def search(self, query_vector, k: int = 5, allowed_ids=None, nprobe=None) -> Tuple[np.ndarray, List[int]]:
         """faiss_store.py:49-81: one query; index rows map to document ids,
         -1 and rows past the id list are dropped; on any error the result is
         ``(np.array([]), [])``.  Any k, as faiss (k > ``FX_MAX_K`` = 1024
@@ -82,12 +106,23 @@ class FAISSVectorStore:
 
         ``allowed_ids`` (document ids; extension): only those documents are
         ranked -- the index's filtered search over their rows (k <=
-        ``FX_MAX_K``), so a narrow filter still returns its k nearest."""
+        ``FX_MAX_K``), so a narrow filter still returns its k nearest.
+
+        ``nprobe`` (extension): search the ``IndexIVFFlat`` of ``build_ivf``
+        over that many lists instead of the whole index (no ``allowed_ids``,
+        k <= ``FX_MAX_K``); without a built one the call fails as any other
+        error here does."""
         try:
             q = query_vector
             if isinstance(q, list):
                 q = np.array(q, dtype=np.float32)
-            if allowed_ids is None:
+            if nprobe is not None:
+                if self.ivf is None:
+                    raise RuntimeError("search(nprobe=...) needs build_ivf first")
+                if allowed_ids is not None:
+                    raise NotImplementedError("search(nprobe=...) takes no allowed_ids")
+                dist, rows = self.ivf.search(q.reshape(1, -1), k, params=_fx.SearchParametersIVF(nprobe=int(nprobe)))
+            elif allowed_ids is None:
                 dist, rows = self.index.search(q.reshape(1, -1), k)
             else:
                 dist, rows = self.index.search(q.reshape(1, -1), k, params=self._rows_selector(allowed_ids))
@@ -140,6 +175,7 @@ class FAISSVectorStore:
             rows = [r for r in range(n_rows) if self.doc_ids[r] in gone]
             if not rows:
                 return 0
+            self.ivf = None
             n = int(self.index.remove_ids(np.asarray(rows, dtype=np.int64)))
             dropped = set(rows)
             self.doc_ids = [doc for r, doc in enumerate(self.doc_ids) if r not in dropped]
@@ -181,6 +217,7 @@ class FAISSVectorStore:
         numbers; errors are logged and raised again."""
         path = filepath or self.index_path
         try:
+            self.ivf = None
             self.index = _fx.read_index(path, dtype=self.dtype, device=self.device)
             if os.path.exists(path + ".mapping"):
                 with open(path + ".mapping", "rb") as f:
@@ -195,6 +232,7 @@ class FAISSVectorStore:
 
     def reset(self):
         """faiss_store.py:124-128: a fresh empty index, no ids."""
+        self.ivf = None
         self.index = _fx.IndexFlatL2(self.dimension, dtype=self.dtype, device=self.device)
         self.doc_ids = []
         logger.info("reset")
