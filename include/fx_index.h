@@ -38,6 +38,9 @@
  *   IndexIVFFlat(q, d,    (a search over nprobe of   faiss_IndexIVFFlat_new_with  fx_ivf_create, fx_ivf_add,
  *     nlist)               nlist inverted lists; see  _metric                      fx_ivf_search
  *                          "inverted file" below)
+ *   IndexScalarQuantizer  (one byte per dimension:   faiss_IndexScalarQuantizer_  fx_sq_create, fx_sq_train,
+ *     (d, QT_8bit)         twice the rows per GPU;    new_with                     fx_sq_add, fx_sq_search
+ *                          "scalar quantizer" below)
  *   index.ntotal          faiss_store.py:53          faiss_Index_ntotal           fx_index_ntotal
  *   (re)IndexFlatL2(d)    faiss_store.py:126         faiss_Index_reset            fx_index_reset
  *   faiss.write_index     faiss_store.py:91,         faiss_write_index_fname      fx_index_write
@@ -619,6 +622,105 @@ int fx_ivf_profile_read(FxIvf* ivf, double* coarse_ms, double* pairs_ms, double*
  * candidate slots per query (nprobe * chunks), queries per pass, and the list
  * scan's launch-grid bound. */
 int fx_ivf_last_plan(FxIvf* ivf, int* path, int* chunks, int* slots, int64_t* q_batch, int64_t* grid);
+
+/* ---- scalar quantizer: faiss IndexScalarQuantizer (8-bit) --------------------
+ *
+ *   faiss (Python)                      faiss C++ / C API                               this ABI
+ *   IndexScalarQuantizer(d, qtype)      faiss_IndexScalarQuantizer_new_with             fx_sq_create
+ *   index.train(x)                      faiss_Index_train                               fx_sq_train
+ *   index.is_trained                    faiss_Index_is_trained                          fx_sq_is_trained
+ *   index.sq.trained                    ScalarQuantizer::trained                        fx_sq_get_trained / _set_trained
+ *   index.add(x)                        faiss_Index_add                                 fx_sq_add
+ *   index.search(x, k)                  faiss_Index_search                              fx_sq_search
+ *   index.reset()                       faiss_Index_reset                               fx_sq_reset
+ *   index.ntotal                        faiss_Index_ntotal                              fx_sq_ntotal
+ *   index.reconstruct_n(i0, n)          faiss_Index_reconstruct_n                       fx_sq_reconstruct_n
+ *   index.reconstruct_batch(keys)       faiss_Index_reconstruct_batch                   fx_sq_reconstruct_batch
+ *   index.sa_encode(x) / sa_decode(c)   faiss_Index_sa_encode / faiss_Index_sa_decode   fx_sq_encode / fx_sq_decode
+ *   (GC of the index)                   faiss_Index_free                                fx_sq_free
+ *
+ * This restates faiss's ScalarQuantizer from memory; it is NOT checked against
+ * a faiss build (as the IxM2 note above).  qtype is faiss's QuantizerType
+ * number: 0 QT_8bit (per dimension, RS_minmax, rangestat_arg 0: vmin_j = min_i
+ * x_ij, vdiff_j = max_i x_ij - vmin_j) or 2 QT_8bit_uniform (one global min and
+ * max, held as the same two arrays with equal entries).  trained is [vmin[d] |
+ * vdiff[d]] in fp32 (QT_8bit_uniform reads back as [vmin, vdiff], 2 floats).
+ *
+ *   encode (fp32, each operation rounded once, no FMA contraction):
+ *     xi = vdiff_j != 0 ? clamp((x_j - vmin_j) / vdiff_j, 0, 1) : 0,  c_j = (int)(255.f * xi) in [0, 255]
+ *   decode:  y_j = vmin_j + ((c_j + 0.5f) / 255.f) * vdiff_j  (two rounded fp32
+ *     operations on the table value: bitwise a numpy fp32 expression)
+ *
+ * The index stores the signed code c' = c - 128 (faiss's byte XOR 0x80, the
+ * int8 MFMA operand) in rows of roundup(d, 128) bytes plus one fp32 constant
+ * per row; fx_sq_encode / fx_sq_decode speak faiss's UNSIGNED bytes [n][d].
+ *
+ * A search has the flat index's contract applied to the DECODED rows: per query
+ * the k rows that minimise sum (x_j - y_j)^2 (L2) or maximise sum x_j y_j (IP)
+ * over the decoded fp32 y, the sum in fp64 rounded once to fp32, ranked by (that
+ * value, row); missing slots I = -1, D = +-FLT_MAX; ids are row numbers in
+ * insertion order.  k <= 32: the fused path (query preparation, the int8 MFMA
+ * scan, exact refine + certification, the exact scan for uncertified queries,
+ * all decided on the device); 32 < k <= FX_MAX_K: the exact scan for the whole
+ * search.  Limitation (as the inverted file's): the exact scan is one fp64 pass
+ * over every decoded row per query, correct but slow, and as k nears 32 more
+ * queries fall to it (at k = 32 every query of an index with 32 rows or more).
+ *
+ * Errors: FX_E_ARG for a null handle, a bad dtype / mem / qtype / metric, add or
+ * search before training, train or set_trained on an index that holds rows,
+ * non-finite training data, k < 1; FX_E_UNSUPPORTED for k > FX_MAX_K and ntotal
+ * >= 2^31; FX_E_INTEGRITY for a host-output search whose candidate lists held
+ * ids outside the index (never in a correct build).  nq == 0 and n == 0 are
+ * FX_OK.
+ *
+ * Out of scope: the 4-bit, 6-bit, fp16 / bf16 and direct qtypes and rangestat
+ * other than min/max; selectors, remove_ids, range_search, IndexIDMap over it,
+ * id offsets; write_index / read_index (faiss's "IxSQ" layout cannot be checked
+ * here); sharding and the search graph; a re-scan stage with wider candidate
+ * lists; IndexIVFScalarQuantizer; scanning with k_scan_v5's ring. */
+typedef struct FxSq FxSq;
+int fx_sq_create(int d, int qtype, int metric, int device, FxSq** out);
+void fx_sq_free(FxSq* sq);
+/* Per-dimension min / max of x [n][d] in one pass (bitwise reproducible).  more
+ * != 0: the call only accumulates (a training set handed over in chunks) and
+ * the index stays untrained; the call with more == 0 finishes.  Any non-finite
+ * input fails the training with FX_E_ARG (the index stays untrained). */
+int fx_sq_train(FxSq* sq, int64_t n, const void* x, int x_dtype, int x_mem, int more);
+int fx_sq_is_trained(const FxSq* sq, int* out);
+/* out / trained: host [2 d] floats, [vmin | vdiff]. */
+int fx_sq_get_trained(FxSq* sq, float* out);
+int fx_sq_set_trained(FxSq* sq, const float* trained);
+/* Ids are the row numbers ntotal .. ntotal + n - 1.  Device x is stream-ordered;
+ * host x blocks. */
+int fx_sq_add(FxSq* sq, int64_t n, const void* x, int x_dtype, int x_mem);
+/* Host results block; device queries and results are stream-ordered. */
+int fx_sq_search(FxSq* sq, int64_t nq, const void* q, int q_dtype, int q_mem, int k, float* D, int64_t* I, int out_mem);
+/* Empties the index, keeps the training. */
+int fx_sq_reset(FxSq* sq);
+int fx_sq_ntotal(const FxSq* sq, int64_t* out);
+/* out [n][d] fp32 (out_mem) <- the decoded rows [i0, i0 + n) / the rows keys[i]
+ * (int64, keys_mem; a key outside [0, ntotal): a row of NaN, as the flat index). */
+int fx_sq_reconstruct_n(FxSq* sq, int64_t i0, int64_t n, float* out, int out_mem);
+int fx_sq_reconstruct_batch(FxSq* sq, int64_t n, const int64_t* keys, int keys_mem, float* out, int out_mem);
+/* sa_encode / sa_decode: x [n][d] (x_dtype) <-> faiss's unsigned codes [n][d],
+ * all three buffers in `mem`. */
+int fx_sq_encode(FxSq* sq, int64_t n, const void* x, int x_dtype, uint8_t* codes, int mem);
+int fx_sq_decode(FxSq* sq, int64_t n, const uint8_t* codes, float* out, int mem);
+int fx_sq_set_stream(FxSq* sq, void* stream);
+/* Of the last search (after a device-output one this synchronises): queries the
+ * refine could not certify (all re-ranked by the exact scan, so both counts are
+ * equal) and candidate ids outside the index (0 in a correct build). */
+int fx_sq_last_counts(FxSq* sq, int64_t* fallbacks, int64_t* exact_fallbacks, int64_t* dropped);
+/* The plan of the last search: path 0 fused / 1 exact, query tiles of a pass,
+ * corpus splits per query tile, splits of the exact scan, queries per pass, and
+ * the scan's workgroups. */
+int fx_sq_last_plan(FxSq* sq, int* path, int* qtiles, int* splits, int* xsplits, int64_t* q_batch, int64_t* grid);
+/* With profiling on, every pass of a search records events around its parts;
+ * _read waits and returns the milliseconds summed since the last read: query
+ * preparation, the scan (exact path: the exact scan), refine + exact fallback,
+ * and the passes they cover. */
+int fx_sq_profile(FxSq* sq, int enable);
+int fx_sq_profile_read(FxSq* sq, double* prep_ms, double* scan_ms, double* refine_ms, int64_t* passes);
 
 /* faiss.write_index / faiss.read_index on the IxF2 format (faiss_store.py:
  * 91,106): fourcc "IxF2", i32 d, i64 ntotal, i64 1<<20, i64 1<<20,

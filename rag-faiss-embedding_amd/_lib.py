@@ -96,6 +96,26 @@ SIGNATURES = {
     "fx_ivf_profile_read": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(_i64)]),
     "fx_ivf_last_plan": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64),
                               ctypes.POINTER(_i64)]),
+    "fx_sq_create": (_i, [_i, _i, _i, _i, _pp]),
+    "fx_sq_free": (None, [_vp]),
+    "fx_sq_train": (_i, [_vp, _i64, _vp, _i, _i, _i]),
+    "fx_sq_is_trained": (_i, [_vp, ctypes.POINTER(_i)]),
+    "fx_sq_get_trained": (_i, [_vp, _vp]),
+    "fx_sq_set_trained": (_i, [_vp, _vp]),
+    "fx_sq_add": (_i, [_vp, _i64, _vp, _i, _i]),
+    "fx_sq_search": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _vp, _i]),
+    "fx_sq_reset": (_i, [_vp]),
+    "fx_sq_ntotal": (_i, [_vp, ctypes.POINTER(_i64)]),
+    "fx_sq_reconstruct_n": (_i, [_vp, _i64, _i64, _vp, _i]),
+    "fx_sq_reconstruct_batch": (_i, [_vp, _i64, _vp, _i, _vp, _i]),
+    "fx_sq_encode": (_i, [_vp, _i64, _vp, _i, _vp, _i]),
+    "fx_sq_decode": (_i, [_vp, _i64, _vp, _vp, _i]),
+    "fx_sq_set_stream": (_i, [_vp, _vp]),
+    "fx_sq_last_counts": (_i, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "fx_sq_last_plan": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i),
+                             ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "fx_sq_profile": (_i, [_vp, _i]),
+    "fx_sq_profile_read": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(_i64)]),
     "fx_index_write": (_i, [_vp, ctypes.c_char_p]),
     "fx_index_read": (_i, [ctypes.c_char_p, _i, _i, _pp]),
     "fx_merge_shards": (_i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -1,6 +1,6 @@
 // fx_device.h -- device-side helpers shared by the HIP translation units
 // (fx_kernels.hip, fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip,
-// fx_select.hip, fx_remove.hip, fx_ivf.hip):
+// fx_select.hip, fx_remove.hip, fx_ivf.hip, fx_sq.hip):
 // conversions, the exact fp64 distance, wave sorts and sums, block placement,
 // the block top-K, the plain scans' tile loop (scan_tiles_128) and the MFMA
 // wrappers of k_scan_v4 / k_scan_v5.  Header-only, all inline.

@@ -557,6 +557,39 @@ struct FxIvf {
     std::mutex mu;
 };
 
+// ---- fx_api_sq.cpp -------------------------------------------------------------
+
+// A scalar-quantizer index (include/fx_index.h, fx_sq.hip): 8-bit signed codes
+// [cap_rows][row_bytes] with a whole tile past the last row, the rows' constants
+// n_c, the trained tables [vmin | vdiff] and the index-wide bound words.
+struct FxSq {
+    int d = 0, qtype = 0, metric = fx::L2, device = 0, row_bytes = 0;
+    int64_t ntotal = 0, cap_rows = 0;
+    bool trained = false;
+    bool train_open = false;  // fx_sq_train calls with more != 0 have accumulated min / max
+    fx::DevArr<char> codes;
+    fx::DevArr<float> nc, tables;
+    fx::DevArr<unsigned> words, mm;
+    fx::DevArr<unsigned long long> bad;
+    hipStream_t own_stream = nullptr, user_stream = nullptr;
+    hipEvent_t switch_ev = nullptr;
+    fx::Options opt;  // (force_fallback of the diagnostic build, read from the environment at creation)
+    // workspace of add / search / the codec
+    fx::DevBuf in, qf32, planes, sigma, eps, rho, shift, cand_d, cand_i, flag, outD, outI, io;
+    fx::DevArr<int> cnt;  // [0] dropped candidate ids, [1] queries flagged, [2] scratch (the exact path's)
+    fx::PinArr<int> pin_cnt;
+    bool counts_pending = false;
+    int64_t last_fallbacks = 0, last_dropped = 0;
+    int last_plan[4] = {0, 0, 0, 0};  // path, query tiles, splits, exact splits
+    int64_t last_qbatch = 0, last_grid = 0;
+    // profiling (fx_sq_profile): 4 events per pass -- start, after the query preparation, after the scan
+    // (exact path: the exact scan), after refine + exact fallback
+    bool profile = false;
+    std::vector<hipEvent_t> ev;
+    std::mutex mu;
+    hipStream_t stream() const { return user_stream ? user_stream : own_stream; }
+};
+
 // A selector (include/fx_index.h): the device image fx_select.hip builds of a
 // subset of `index`'s rows [0, ntotal) as they were at creation.
 struct FxSelector {

@@ -1,5 +1,5 @@
 // fx_internal.h -- shared between the HIP translation units (fx_kernels.hip,
-// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip, fx_kmeans.hip, fx_ivf.hip) and the host C ABI
+// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip, fx_kmeans.hip, fx_ivf.hip, fx_sq.hip) and the host C ABI
 // (fx_index.cpp, fx_api_*.cpp, fx_plan.cpp; their own header: fx_host.h):
 // tiling constants, kernel parameter blocks, the launchers' prototypes and
 // their host-side helpers.  Not part of the public ABI (include/fx_index.h).
@@ -564,6 +564,102 @@ hipError_t launch_mu(const char* codes, int dt, int row_bytes, int d, int64_t n,
 // |y|^2), their maximum -> cmax_bits (atomicMax)
 hipError_t launch_centre_norms(const char* codes, int dt, int row_bytes, int64_t r0, int64_t r1, const float* mu,
                                float* cnorms, unsigned* cmax_bits, hipStream_t s);
+// scalar quantizer (fx_sq.hip): faiss's IndexScalarQuantizer with 8-bit codes.
+// trained = [vmin[d] | vdiff[d]] fp32.  A stored row is row_bytes = roundup(d,
+// 128) signed codes c' = c - 128 (padding 0); nc[row] = sum_j (s_j c'_j)^2 with
+// s_j = vdiff_j / 255 (fp64 sum, rounded once).
+constexpr int SQ_P = 3;          // int8 digit planes of the query operand
+constexpr int SQ_STAGE_B = 64;   // bytes of each row's K staged per pipeline stage (one MFMA k-chunk)
+constexpr int SQ_EXACT_GRID = 1024, SQ_MERGE_GRID = 256;
+// index-wide constants on the device: float bits of max n_c, the integer max
+// sum c'^2, float bits of rho_dec (the decode's rounding: |y_fp32 - (m + s c')|
+// over any row), 1 word spare
+enum { SQ_W_MAXNC = 0, SQ_W_MAXC2 = 1, SQ_W_RHO = 2, SQ_WORDS = 4 };
+// mm = [min[d] | max[d]] as order-preserving uints (0xffffffff / 0 before the
+// first row); *bad counts non-finite inputs
+hipError_t launch_sq_minmax(const void* x, int x_dt, int64_t n, int d, unsigned* mm, unsigned long long* bad,
+                            hipStream_t s);
+hipError_t launch_sq_minmax_reset(unsigned* mm, int d, unsigned long long* bad, hipStream_t s);
+// trained <- mm (uniform != 0: one global min / max in every entry)
+hipError_t launch_sq_finish(const unsigned* mm, int d, int uniform, float* trained, hipStream_t s);
+// words[SQ_W_RHO] <- the decode rounding bound of `trained`
+hipError_t launch_sq_consts(const float* trained, int d, unsigned* words, hipStream_t s);
+// rows x [n][d] -> signed codes at codes_row0 (stride row_bytes, padding
+// zeroed), their n_c, and the two running maxima
+hipError_t launch_sq_encode(const void* x, int x_dt, int64_t n, int d, const float* trained, int row_bytes,
+                            char* codes_row0, float* nc_row0, unsigned* words, hipStream_t s);
+// rows x [n][d] -> faiss's unsigned bytes [n][d]
+hipError_t launch_sq_encode_u8(const void* x, int x_dt, int64_t n, int d, const float* trained, uint8_t* out,
+                               hipStream_t s);
+// out[i][0..d) fp32 <- decode of source row r_i: keys null: r_i = key0 + i; flip
+// = 0x80 for caller bytes [.][stride] of faiss's unsigned codes, 0 for stored
+// rows.  A key outside [0, nrows): a row of all-ones bits (NaN), nothing read.
+hipError_t launch_sq_decode(const char* codes, int stride, int flip, int64_t nrows, const int64_t* keys, int64_t key0,
+                            int64_t n, int d, const float* trained, float* out, hipStream_t s);
+struct SqPrep {
+    const void* q;        // [nq][d] on the device
+    int q_dt, metric, d, row_bytes;
+    int64_t nq, nq_pad;
+    const float* trained;
+    const unsigned* words;
+    float* qf32;          // [nq_pad][row_bytes] fp32 queries, zero padded
+    char* planes;         // [SQ_P][nq_pad][row_bytes]
+    float* sigma;         // [nq_pad]
+    float* qeps;          // [nq] E
+    float* qrho;          // [nq] rho' = |w - w_op| (reported; the bound uses it inside E)
+    double* qshift;       // [nq] |z|^2 (L2), -x.m (IP): scan key + shift estimates the exact key
+    int* zero[2];         // counters set to 0 (flagged, dropped)
+};
+hipError_t launch_sq_prep(const SqPrep& p, hipStream_t s);
+struct SqScan {
+    const char* codes;
+    const float* nc;
+    int64_t ntotal;
+    int row_bytes;
+    const char* planes;
+    const float* sigma;
+    int64_t nq, nq_pad;
+    int n_qtiles, n_ctiles, splits;
+    float* cand_d;        // [n_qtiles][splits][TILE_Q][KP]
+    int* cand_i;
+};
+hipError_t launch_sq_scan(int metric, const SqScan& p, hipStream_t s);
+struct SqRefine {
+    const float* cand_d;
+    const int* cand_i;
+    int splits;
+    int64_t nq, ntotal;
+    int k, d, row_bytes;
+    const char* codes;
+    const float* trained;
+    const unsigned* words;
+    const float* qf32;
+    const float* qeps;
+    const double* qshift;
+    float* D;
+    int64_t* I;
+    int* n_flag;          // [0] count, [1 ..] flagged queries
+    int* n_drop;
+    int force_fb;
+};
+hipError_t launch_sq_refine(int metric, const SqRefine& p, hipStream_t s);
+// k_sq_exact + k_sq_merge for the queries n_flag[1 ..] (count n_flag[0], read on
+// the device): item (flagged f, split c of xs) -> cd / ci[item][k], merged under
+// (key, row) -> D / I
+struct SqExact {
+    const char* codes;
+    int row_bytes, d;
+    int64_t ntotal;
+    const float* trained;
+    const float* qf32;
+    const int* n_flag;
+    int k, xs;
+    float* cd;
+    int* ci;
+    float* D;
+    int64_t* I;
+};
+hipError_t launch_sq_exact(int metric, const SqExact& p, hipStream_t s);
 hipError_t launch_synth(void* out, int64_t row0, int64_t n, int d, int dtype, uint64_t seed,
                         hipStream_t s);
 hipError_t launch_to_f32(const void* codes, int st_dt, int row_bytes, int64_t n, int d, float* out,

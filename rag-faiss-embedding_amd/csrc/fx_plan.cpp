@@ -210,6 +210,42 @@ IvfPlan plan_ivf(int64_t nq, int nprobe_eff, int64_t nlist, int64_t max_list_row
     return P;
 }
 
+SqPlan plan_sq(int64_t nq, int64_t ntotal, int k, int row_bytes) {
+    // row_bytes is part of the signature but does not enter today: a tile's cost does not change how
+    // many workgroups fill the CUs
+    (void)row_bytes;
+    SqPlan P;
+    P.path = k <= KP ? SQ_PATH_FUSED : SQ_PATH_EXACT;
+    nq = std::max<int64_t>(nq, 1);
+    const int nct = (int)std::max<int64_t>(1, (ntotal + TILE_R - 1) / TILE_R);
+    const int xs = (int)std::max<int64_t>(1, std::min<int64_t>(64, ntotal / 1024));
+    if (P.path == SQ_PATH_EXACT) {
+        P.xsplits = xs;
+        P.splits = 1;
+        P.q_batch = std::max<int64_t>(1, std::min<int64_t>(nq, SQ_CAND_BYTES / ((int64_t)xs * k * 8)));
+        P.qtiles = (int)((P.q_batch + TILE_Q - 1) / TILE_Q);
+        P.grid = SQ_EXACT_GRID;
+        P.cand_bytes = P.q_batch * xs * k * 8;
+        return P;
+    }
+    constexpr int min_tiles = 3;
+    const int64_t per_list = (int64_t)TILE_Q * KP * 8;
+    int64_t qb = nq;
+    for (;;) {
+        const int ntl = (int)((qb + TILE_Q - 1) / TILE_Q);
+        const int splits = fill_splits(ntl, ntl, nct, min_tiles);
+        P.qtiles = ntl;
+        P.splits = splits;
+        P.q_batch = qb;
+        P.cand_bytes = (int64_t)ntl * splits * per_list;
+        if (P.cand_bytes <= SQ_CAND_BYTES || ntl == 1) break;
+        qb = (int64_t)(ntl / 2) * TILE_Q;
+    }
+    P.xsplits = std::min(P.splits, xs);
+    P.grid = (int64_t)P.qtiles * P.splits;
+    return P;
+}
+
 bool plan_remove(const KeptPrefix& P, int64_t stage_rows, std::vector<RemoveChunk>& out) {
     const int64_t g = P.g, nt = P.ntotal;
     const int64_t nb = (nt + g - 1) / g;  // boundary i is row min(nt, i g)

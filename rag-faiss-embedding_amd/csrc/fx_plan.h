@@ -77,6 +77,28 @@ constexpr int64_t IVF_CAND_BYTES = 1ll << 30;
 IvfPlan plan_ivf(int64_t nq, int nprobe_eff, int64_t nlist, int64_t max_list_rows, int64_t ntotal, int k,
                  int row_bytes);
 
+// ---- scalar quantizer (fx_sq.hip): the plan of one IndexScalarQuantizer search
+
+// path: the fused int8 MFMA scan + refine (k <= KP), or the exact scan
+// (k_sq_exact) for the whole search.
+enum { SQ_PATH_FUSED = 0, SQ_PATH_EXACT = 1 };
+struct SqPlan {
+    int path = SQ_PATH_FUSED;
+    int qtiles = 1;       // query tiles of a full pass: ceil(q_batch / 128)
+    int splits = 1;       // corpus splits per query tile (fused), <= corpus tiles
+    int xsplits = 1;      // corpus splits per query of the exact scan: the whole search on the exact
+                          // path, the flagged queries on the fused one (then <= splits, so that the
+                          // fused pass's candidate buffer holds them)
+    int64_t q_batch = 1;  // queries per pass
+    int64_t grid = 0;     // workgroups of a full pass's scan (fused: qtiles * splits; exact: the fixed grid)
+    int64_t cand_bytes = 0;  // candidate bytes of a full pass (entries of 8 B: key + row)
+};
+constexpr int64_t SQ_CAND_BYTES = 1ll << 30;
+// Fused: the splits of fill_splits (>= 3 tiles each, whole rounds of 256 CUs, ~1,024 workgroups for a
+// small batch), and the most queries per pass whose [qtile][split][128][KP] lists fit SQ_CAND_BYTES.
+// Exact: up to 64 splits of >= 1,024 rows, and the most queries whose [query][xsplit][k] lists fit.
+SqPlan plan_sq(int64_t nq, int64_t ntotal, int k, int row_bytes);
+
 // ---- remove_ids (fx_remove.hip): the host's chunk plan ----------------------
 
 // Kept rows before row r, for the rows the plan asks about: any row (the

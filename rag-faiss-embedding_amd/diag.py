@@ -29,6 +29,13 @@ class IndexFlatIP(_faiss.IndexFlatIP):
     _lib = lib
 
 
+class IndexScalarQuantizer(_faiss.IndexScalarQuantizer):
+    """``force_fallback`` comes from ``FX_FORCE_FALLBACK`` in the environment
+    when the index is created (it has no option table of its own)."""
+
+    _lib = lib
+
+
 def read_index(path: str, dtype: str = "float32", device: int = 0) -> IndexFlatL2:
     h = ctypes.c_void_p()
     _lib.check(lib.fx_index_read(str(path).encode(), _faiss._DTYPES[dtype], int(device), ctypes.byref(h)), lib)

@@ -33,6 +33,7 @@ class FAISSVectorStore:
     _instance = None
     _initialized = False
     ivf = None  # the IndexIVFFlat over the store's rows (build_ivf); dropped by every call that changes the rows
+    sq = None   # the IndexScalarQuantizer over the store's rows (build_sq); dropped by the same calls
 
     def __new__(cls, *args, **kwargs):
         if cls._instance is None:
@@ -63,7 +64,7 @@ class FAISSVectorStore:
         """faiss_store.py:36-47.  The ids are recorded before the rows go in,
         and their count is not checked against the rows (as there)."""
         rows = self._as_rows(vectors)
-        self.ivf = None
+        self.ivf = self.sq = None
         self.doc_ids.extend(ids)
         self.index.add(rows)
         logger.info("add: %d ids -> ntotal %d", len(ids), self.index.ntotal)
@@ -98,7 +99,26 @@ class FAISSVectorStore:
             logger.error("build_ivf failed: %s", e)
             raise
 
-    def search(self, query_vector, k: int = 5, allowed_ids=None, nprobe=None) -> Tuple[np.ndarray, List[int]]:
+    def build_sq(self, qtype: int = _fx.ScalarQuantizer.QT_8bit):
+        """An ``IndexScalarQuantizer`` over the store's rows (extension): one
+        byte per dimension, trained on and filled from the store's own index
+        on the device.  Ids are row numbers, so ``doc_ids`` keeps mapping
+        results.  Kept as ``self.sq`` until a call changes the rows;
+        ``search(..., sq=True)`` uses it.  Errors are logged and raised again,
+        as in ``load_index``."""
+        try:
+            sq = _fx.IndexScalarQuantizer(self.dimension, qtype, _fx.METRIC_L2, device=self.device)
+            sq.train(self.index)
+            sq.add_from_index(self.index)
+            self.sq = sq
+            logger.info("build_sq: %d rows, %d bytes per row", self.index.ntotal, sq.code_size)
+            return sq
+        except Exception as e:
+            logger.error("build_sq failed: %s", e)
+            raise
+
+    def search(self, query_vector, k: int = 5, allowed_ids=None, nprobe=None, sq: bool = False
+               ) -> Tuple[np.ndarray, List[int]]:
         """faiss_store.py:49-81: one query; index rows map to document ids,
         -1 and rows past the id list are dropped; on any error the result is
         ``(np.array([]), [])``.  Any k, as faiss (k > ``FX_MAX_K`` = 1024
@@ -111,12 +131,22 @@ class FAISSVectorStore:
         ``nprobe`` (extension): search the ``IndexIVFFlat`` of ``build_ivf``
         over that many lists instead of the whole index (no ``allowed_ids``,
         k <= ``FX_MAX_K``); without a built one the call fails as any other
-        error here does."""
+        error here does.
+
+        ``sq=True`` (extension): search the ``IndexScalarQuantizer`` of
+        ``build_sq`` -- the k nearest DECODED rows (no ``allowed_ids``, no
+        ``nprobe``, k <= ``FX_MAX_K``)."""
         try:
             q = query_vector
             if isinstance(q, list):
                 q = np.array(q, dtype=np.float32)
-            if nprobe is not None:
+            if sq:
+                if self.sq is None:
+                    raise RuntimeError("search(sq=True) needs build_sq first")
+                if allowed_ids is not None or nprobe is not None:
+                    raise NotImplementedError("search(sq=True) takes no allowed_ids and no nprobe")
+                dist, rows = self.sq.search(q.reshape(1, -1), k)
+            elif nprobe is not None:
                 if self.ivf is None:
                     raise RuntimeError("search(nprobe=...) needs build_ivf first")
                 if allowed_ids is not None:
@@ -175,7 +205,7 @@ class FAISSVectorStore:
             rows = [r for r in range(n_rows) if self.doc_ids[r] in gone]
             if not rows:
                 return 0
-            self.ivf = None
+            self.ivf = self.sq = None
             n = int(self.index.remove_ids(np.asarray(rows, dtype=np.int64)))
             dropped = set(rows)
             self.doc_ids = [doc for r, doc in enumerate(self.doc_ids) if r not in dropped]
@@ -217,7 +247,7 @@ class FAISSVectorStore:
         numbers; errors are logged and raised again."""
         path = filepath or self.index_path
         try:
-            self.ivf = None
+            self.ivf = self.sq = None
             self.index = _fx.read_index(path, dtype=self.dtype, device=self.device)
             if os.path.exists(path + ".mapping"):
                 with open(path + ".mapping", "rb") as f:
@@ -232,7 +262,7 @@ class FAISSVectorStore:
 
     def reset(self):
         """faiss_store.py:124-128: a fresh empty index, no ids."""
-        self.ivf = None
+        self.ivf = self.sq = None
         self.index = _fx.IndexFlatL2(self.dimension, dtype=self.dtype, device=self.device)
         self.doc_ids = []
         logger.info("reset")
