@@ -437,6 +437,19 @@ int fx_ivf_search(FxIvf* v, int64_t nq, const void* q, int q_dtype, int q_mem, i
         if (v->profile) HIP_TRY(hipEventRecord(ev[2], s));
         HIP_TRY(launch_ivf_scan(p->dtype, p->metric, sc, s));
         if (v->profile) HIP_TRY(hipEventRecord(ev[3], s));
+#ifdef FX_DIAG
+        // FX_IVF_CAND (read when the index was created): the pass's scan lists, probed lists and list
+        // offsets appended to the file, before the refine reads the lists and the exact scan writes over them:
+        //   cand_d, cand_i [qb][slots][KP] | coarse [qb][np] i64 | list_off [nlist + 1]
+        if (!p->opt.ivf_cand.empty()) {
+            const std::string& path = p->opt.ivf_cand;
+            HIP_TRY(hipStreamSynchronize(s));
+            HIP_TRY(dump_device<float>(path, sc.cand_d, (size_t)qb * slots * KP));
+            HIP_TRY(dump_device<int>(path, sc.cand_i, (size_t)qb * slots * KP));
+            HIP_TRY(dump_device<int64_t>(path, ex.coarse, (size_t)qb * np));
+            HIP_TRY(dump_device<int>(path, v->list_off, (size_t)v->nlist + 1));
+        }
+#endif
         // 4. refine + certification over the query's slots (one "query tile" per query)
         RefineParams rp{};
         rp.cand_d = sc.cand_d;

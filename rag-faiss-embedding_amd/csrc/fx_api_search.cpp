@@ -383,20 +383,6 @@ hipError_t enqueue_fallback(FxIndex* h, SearchPlan& P, hipStream_t s) {
                                  s, P.sel ? P.sel->mask : nullptr, P.rp.labels);
 }
 
-#ifdef FX_DIAG
-template <typename T>
-hipError_t dump_device(const std::string& path, const void* dev, size_t n) {
-    std::vector<T> v(n);
-    hipError_t e = hipMemcpy(v.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return e;
-    if (FILE* f = fopen(path.c_str(), "ab")) {
-        fwrite(v.data(), sizeof(T), n, f);
-        fclose(f);
-    }
-    return hipSuccess;
-}
-#endif
-
 }  // namespace
 
 // a host-output search whose refine dropped candidate ids outside [0, ntotal)

@@ -363,6 +363,25 @@ int fx_sq_search(FxSq* h, int64_t nq, const void* q, int q_dtype, int q_mem, int
         sc.cand_i = ex.ci;
         HIP_TRY(launch_sq_scan(h->metric, sc, s));
         if (h->profile) HIP_TRY(hipEventRecord(ev[2], s));
+#ifdef FX_DIAG
+        // FX_SQ_CAND: the pass's scan lists, query operands and the index's constants appended to the
+        // file, before the refine reads the lists and the exact scan writes over them:
+        //   cand_d, cand_i [qtiles][splits][128][KP] | sigma [nq_pad] | qeps [nq] | qshift [nq] f64 |
+        //   planes [3][nq_pad][row_bytes] | words [SQ_WORDS] | n_c [ntotal]
+        if (!h->opt.sq_cand.empty()) {
+            const std::string& path = h->opt.sq_cand;
+            const size_t ncand = (size_t)sc.n_qtiles * P.splits * TILE_Q * KP;
+            HIP_TRY(hipStreamSynchronize(s));
+            HIP_TRY(dump_device<float>(path, sc.cand_d, ncand));
+            HIP_TRY(dump_device<int>(path, sc.cand_i, ncand));
+            HIP_TRY(dump_device<float>(path, pp.sigma, (size_t)nq_pad));
+            HIP_TRY(dump_device<float>(path, pp.qeps, (size_t)qb));
+            HIP_TRY(dump_device<double>(path, pp.qshift, (size_t)qb));
+            HIP_TRY(dump_device<char>(path, pp.planes, (size_t)SQ_P * nq_pad * rb));
+            HIP_TRY(dump_device<unsigned>(path, h->words, (size_t)SQ_WORDS));
+            HIP_TRY(dump_device<float>(path, h->nc, (size_t)h->ntotal));
+        }
+#endif
         // 3. refine + certification; every split pruned only with its own KP-th key
         SqRefine rp{};
         rp.cand_d = sc.cand_d;

@@ -185,6 +185,7 @@ struct Options {
     int force_fallback = 0;  // FX_FORCE_FALLBACK: flag every query (1: -> re-scan, 2: -> exact scan)
     int scan_dbg = 0;        // FX_SCAN_DBG: ablation switches of -DFX_ABLATION builds / key dump (32)
     std::string trace, stamps, cand, keys;  // FX_SCAN_TRACE / _STAMPS / _CAND / _KEYS dump paths
+    std::string sq_cand, ivf_cand;  // FX_SQ_CAND / FX_IVF_CAND: the scan lists of fx_sq_search / fx_ivf_search, per pass
 #else
     static constexpr int force_fallback = 0, scan_dbg = 0;
 #endif
@@ -231,6 +232,8 @@ struct Options {
         str("FX_SCAN_STAMPS", stamps);
         str("FX_SCAN_CAND", cand);
         str("FX_SCAN_KEYS", keys);
+        str("FX_SQ_CAND", sq_cand);
+        str("FX_IVF_CAND", ivf_cand);
 #endif
     }
     // option name -> its slot and accepted range [lo, hi] (allowed: a value
@@ -290,6 +293,22 @@ struct Options {
         return nullptr;
     }
 };
+
+#ifdef FX_DIAG
+// n elements of device memory appended to the file `path` (the diagnostic dumps; the caller has
+// synchronised the stream that wrote them)
+template <typename T>
+hipError_t dump_device(const std::string& path, const void* dev, size_t n) {
+    std::vector<T> v(n);
+    hipError_t e = hipMemcpy(v.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    if (FILE* f = fopen(path.c_str(), "ab")) {
+        fwrite(v.data(), sizeof(T), n, f);
+        fclose(f);
+    }
+    return hipSuccess;
+}
+#endif
 
 // scan image of the index (what the MFMA scan streams, and its row constants)
 enum ImageKind {

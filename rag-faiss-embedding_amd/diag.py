@@ -5,8 +5,20 @@ compiled under ``-DFX_DIAG`` (``make -C csrc diag``): its option table adds
 the test hooks the product library does not carry -- ``force_fallback``
 (1: every query through the device-gated re-scan, 2: through the exact fp64
 scan) and ``scan_dbg`` 32 (the scan's whole key matrix dumped to
-``FX_SCAN_KEYS``) -- plus the FX_SCAN_TRACE / _CAND dumps.  The classes here
-are the faiss.py ones with every call going to that build.
+``FX_SCAN_KEYS``) -- plus the FX_SCAN_TRACE / _CAND dumps, and two dumps of
+the newer scans' lists, written per pass before the refine reads them and the
+exact path writes over them (paths read when the index is created):
+
+``FX_SQ_CAND``   fx_sq_search: ``cand_d``, ``cand_i`` [qtiles][splits][128][KP],
+                 ``sigma`` [nq_pad], ``E`` [nq], the shift [nq] f64, the digit
+                 planes [3][nq_pad][row_bytes] i8, the index words [4] u32
+                 (max n_c, max sum c'^2, rho_dec as float bits, 0) and the
+                 rows' ``n_c`` [ntotal] (tests/test_sq_scan_parity.py)
+``FX_IVF_CAND``  fx_ivf_search: ``cand_d``, ``cand_i`` [nq][slots][KP], the
+                 probed lists [nq][nprobe] i64, ``list_off`` [nlist + 1] i32
+                 (tests/test_ivf_scan_parity.py)
+
+The classes here are the faiss.py ones with every call going to that build.
 """
 from __future__ import annotations
 
@@ -34,6 +46,16 @@ class IndexScalarQuantizer(_faiss.IndexScalarQuantizer):
     when the index is created (it has no option table of its own)."""
 
     _lib = lib
+
+
+class IndexIVFFlat(_faiss.IndexIVFFlat):
+    """An inverted file lives in the build of its quantizer: this one takes a
+    quantizer of this module.  ``FX_IVF_CAND`` comes from the environment when
+    the index is created; ``force_fallback`` is the quantizer's option."""
+
+    def __init__(self, quantizer, *args, **kwargs):
+        assert quantizer._lib is lib, "the quantizer must be an index of the diagnostic build"
+        super().__init__(quantizer, *args, **kwargs)
 
 
 def read_index(path: str, dtype: str = "float32", device: int = 0) -> IndexFlatL2:

@@ -1,7 +1,8 @@
 """numpy restatement of the scalar quantizer (include/fx_index.h "scalar
 quantizer"): train / encode / decode in fp32 with every operation rounded once,
 and search as the oracle's exact k-NN over the decoded rows.  Inputs are rounded
-to fp32 first.  Also the two clustered corpora the model and GPU tests share."""
+to fp32 first.  Also the corpora the model and GPU tests share: the two clustered ones
+and the box-corner corpus that drives the int8 accumulators past 2^24."""
 import numpy as np
 
 from oracle import flat_l2 as O
@@ -63,6 +64,32 @@ def search(xq, decoded, k, metric=O.METRIC_L2):
         Di, Ii = knn(xq[i:i + 1], decoded[cand], k)
         D[i], I[i] = Di[0], cand[Ii[0]]
     return D, I
+
+
+def corner_corpus(n, nq, d=1100, ncorner=16, seed=3):
+    """A corpus whose int8 dots pass 2^24 (possible from d = 1,033 on).
+
+    Rows: standard normal clipped to [-3, 3], with 2 ncorner of them (spread over the whole
+    corpus) replaced by the box corners +-3 sgn_i, sgn_i random signs per dimension.  Every
+    dimension then trains to vmin = -3, vdiff = 6, and a corner row is all codes 127 / -128.
+    Queries: (2.5 +- 0.05) sgn_i, jittered per dimension (first digits |h1| of 118 .. 123 under the
+    scale 2^-11 that |x| <= 2.63 keeps: against +-3 sgn_i the first plane's dot is ~ 120.5 * 127.5 *
+    d = 1.007 * 2^24 at d = 1100, odd as often as even -- the unjittered 2.5 sgn_i gives an inner-
+    product query 120 in every dimension and only even dots), then 3 sgn_i, then the jittered
+    queries negated; the rest standard normal.  Needs nq >= 3 ncorner and n >= 2 ncorner."""
+    assert nq >= 3 * ncorner and n >= 2 * ncorner
+    rng = np.random.default_rng(seed)
+    sgn = rng.choice(np.array([-1.0, 1.0], dtype=f32), size=(ncorner, d))
+    assert np.unique(sgn, axis=0).shape[0] == ncorner
+    xb = np.clip(rng.standard_normal((n, d)), -3.0, 3.0).astype(f32)
+    at = np.linspace(0, n - 1, 2 * ncorner).astype(np.int64)  # first and last row included
+    xb[at[0::2]] = f32(3) * sgn
+    xb[at[1::2]] = f32(-3) * sgn
+    xq = rng.standard_normal((nq, d)).astype(f32)
+    xq[:ncorner] = (2.5 + 0.05 * rng.uniform(-1.0, 1.0, size=(ncorner, d))).astype(f32) * sgn
+    xq[ncorner:2 * ncorner] = f32(3) * sgn
+    xq[2 * ncorner:3 * ncorner] = -xq[:ncorner]
+    return xb, xq
 
 
 def clustered(spread, d=384, n=20000, nq=256, seed=0, ncentres=64):

@@ -75,10 +75,21 @@ def prep(xq, s, m, metric_l2, M2, c2max, rho_dec):
     return (h1.astype(np.int64), h2.astype(np.int64), h3.astype(np.int64)), sg.astype(np.float32), shift, E
 
 
+def int_dots(planes, cs):
+    """The three i32 accumulators of every (query, row): exact integer dots."""
+    return [(h @ cs.T) for h in planes]
+
+
+def inexact_conversions(a):
+    """Entries of an accumulator past the fp32 integer range (|a| > 2^24) that f32(a) rounds."""
+    a = np.asarray(a)
+    return int(((np.abs(a) > 2 ** 24) & (a.astype(np.float32).astype(np.float64) != a.astype(np.float64))).sum())
+
+
 def scan_keys(planes, sg, cs, nc, metric_l2):
     """k_sq_scan's epilogue in fp32: exact integer dots, f32(acc) conversions,
     two fused multiply-adds by powers of two, one for the key."""
-    a = [(h @ cs.T) for h in planes]
+    a = int_dots(planes, cs)
     f = [x.astype(np.float32) for x in a]
     t1 = (f[1].astype(np.float64) / 256.0 + f[0].astype(np.float64)).astype(np.float32)      # fmaf: one rounding
     t2 = (f[2].astype(np.float64) / 65536.0 + t1.astype(np.float64)).astype(np.float32)
@@ -161,3 +172,23 @@ def test_key_within_the_bound_past_the_exact_accumulator_range():
     for metric_l2 in (True, False):
         _, _, err, bound, _, _, _ = run_model(xb, xq, metric_l2)
         assert (err <= bound).all()
+
+
+@pytest.mark.parametrize("metric_l2", [True, False], ids=["L2", "IP"])
+def test_key_within_the_bound_where_an_accumulator_passes_2_24(metric_l2):
+    """The standard normal rows of the test above stay 36 times short of 2^24 (max |a| ~ 4.6e5), so
+    f32(acc) never rounds there.  tests/_sq_ref.corner_corpus does pass it: the precondition asserted
+    first is a (query, row) pair with |a1| > 2^24 whose fp32 conversion is inexact, the 6 u A term of
+    the bound."""
+    xb, xq = R.corner_corpus(2000, 48)
+    trained = R.train(xb)
+    s, m, cs, nc, M2, c2max, rho_dec = index_consts(trained, R.encode(xb, trained))
+    planes, _, _, _ = prep(xq, s, m, metric_l2, M2, c2max, rho_dec)
+    a = int_dots(planes, cs)
+    amax = [int(np.abs(x).max()) for x in a]
+    rounded = inexact_conversions(a[0])
+    print(f"{'L2' if metric_l2 else 'IP'}: max |a1|, |a2|, |a3| = {amax}, f32(a1) != a1 for {rounded} of {a[0].size} pairs")
+    assert amax[0] > 2 ** 24 and rounded >= 1, "the corpus does not reach the accumulator's inexact fp32 range"
+    keys, exact, err, bound, shift, E, rho = run_model(xb, xq, metric_l2)
+    print(f"worst error / bound {float((err / bound).max()):.3f}")
+    assert (err <= bound).all()
