@@ -41,6 +41,10 @@
  *   IndexScalarQuantizer  (one byte per dimension:   faiss_IndexScalarQuantizer_  fx_sq_create, fx_sq_train,
  *     (d, QT_8bit)         twice the rows per GPU;    new_with                     fx_sq_add, fx_sq_search
  *                          "scalar quantizer" below)
+ *   IndexIVFScalarQuant-  (both: nprobe lists of     faiss_IndexIVFScalarQuant-   fx_ivfsq_create, fx_ivfsq_train,
+ *     izer(q, d, nlist,    one byte per dimension;    izer_new_with_metric         fx_ivfsq_add, fx_ivfsq_search
+ *     QT_8bit)             "inverted file over 8-bit
+ *                          codes" below)
  *   index.ntotal          faiss_store.py:53          faiss_Index_ntotal           fx_index_ntotal
  *   (re)IndexFlatL2(d)    faiss_store.py:126         faiss_Index_reset            fx_index_reset
  *   faiss.write_index     faiss_store.py:91,         faiss_write_index_fname      fx_index_write
@@ -576,8 +580,8 @@ int fx_kmeans_profile_read(FxIndex* centroids, double* assign_ms, double* sort_m
  * Out of scope: writing / reading an IVF index (faiss's "IwFl" layout cannot
  * be checked here: persist the quantizer as IxF2 and re-add the rows),
  * remove_ids, range_search, selectors, reconstruct*, search_preassigned,
- * sharding across GPUs, the search graph, IndexIVFPQ /
- * IndexIVFScalarQuantizer. */
+ * sharding across GPUs, the search graph, IndexIVFPQ (8-bit lists:
+ * "inverted file over 8-bit codes" below). */
 typedef struct FxIvf FxIvf;
 int fx_ivf_create(FxIndex* quantizer, int d, int64_t nlist, int storage_dtype, int metric, FxIvf** out);
 void fx_ivf_free(FxIvf* ivf);
@@ -677,7 +681,8 @@ int fx_ivf_last_plan(FxIvf* ivf, int* path, int* chunks, int* slots, int64_t* q_
  * other than min/max; selectors, remove_ids, range_search, IndexIDMap over it,
  * id offsets; write_index / read_index (faiss's "IxSQ" layout cannot be checked
  * here); sharding and the search graph; a re-scan stage with wider candidate
- * lists; IndexIVFScalarQuantizer; scanning with k_scan_v5's ring. */
+ * lists; scanning with k_scan_v5's ring (8-bit codes in inverted lists:
+ * "inverted file over 8-bit codes" below). */
 typedef struct FxSq FxSq;
 int fx_sq_create(int d, int qtype, int metric, int device, FxSq** out);
 void fx_sq_free(FxSq* sq);
@@ -721,6 +726,100 @@ int fx_sq_last_plan(FxSq* sq, int* path, int* qtiles, int* splits, int* xsplits,
  * and the passes they cover. */
 int fx_sq_profile(FxSq* sq, int enable);
 int fx_sq_profile_read(FxSq* sq, double* prep_ms, double* scan_ms, double* refine_ms, int64_t* passes);
+
+/* ---- inverted file over 8-bit codes: faiss IndexIVFScalarQuantizer ------------
+ *
+ *   faiss (Python)                               faiss C++ / C API                          this ABI
+ *   IndexIVFScalarQuantizer(quantizer, d, nlist, faiss_IndexIVFScalarQuantizer_new_with_    fx_ivfsq_create
+ *       qtype, metric, by_residual)                  metric
+ *   index.train(x)                               faiss_Index_train                          the k-means calls above and fx_index_add
+ *                                                                                           on the quantizer, then fx_ivfsq_train
+ *   index.is_trained                             faiss_Index_is_trained                     fx_ivfsq_is_trained (and the quantizer's rows)
+ *   index.sq.trained                             ScalarQuantizer::trained                   fx_ivfsq_get_trained / _set_trained
+ *   index.add(x) / add_with_ids(x, ids)          faiss_Index_add / _add_with_ids            fx_ivfsq_add
+ *   index.nprobe; index.search(x, k)             faiss_IndexIVF_set_nprobe / _Index_search  fx_ivfsq_search
+ *   index.reset()                                faiss_Index_reset                          fx_ivfsq_reset
+ *   index.ntotal                                 faiss_Index_ntotal                         fx_ivfsq_ntotal
+ *   invlists.list_size(l) / get_ids(l)           faiss_IndexIVF_get_list_size / ..get_ids   fx_ivfsq_list_sizes / _list_ids
+ *   invlists.get_codes(l)                        InvertedLists::get_codes                   fx_ivfsq_list_codes
+ *   (GC of the index)                            faiss_Index_free                           fx_ivfsq_free
+ *
+ * Like the two sections it joins ("inverted file", "scalar quantizer"), this
+ * restates faiss from memory and is NOT checked against a faiss build.  One
+ * difference is known and deliberate: faiss ranks a row of list l by
+ * |fl(x - c_l) - decode(code)|^2 (the distance between residuals), while this
+ * contract ranks by the decoded row that reconstruct would return, below.
+ *
+ * Lists.  The quantizer is a borrowed unlabelled flat index; a row's list is its
+ * exact k = 1 search; rows are kept in list order and regrouped by the next
+ * search (or list accessor) after an add; ids are sequential or the caller's
+ * int64; the probe set of a query is quantizer.search(q, min(nprobe, nlist)):
+ * all as the "inverted file" section says.
+ *
+ * Encoding.  qtype is 0 QT_8bit or 2 QT_8bit_uniform.  With by_residual != 0
+ * (faiss's default) the encoded vector of a row of list l is r = fl32(x - c_l),
+ * one rounded fp32 subtraction per dimension against the fp32 centroid the
+ * quantizer reconstructs (as it was when the tables were trained); otherwise r =
+ * x.  The code is the "scalar quantizer" section's encode(r), bitwise.  The
+ * tables [vmin | vdiff] are one min / max pass over the r of the training rows.
+ *
+ * Decoded row.  y = fl32(c_l + decode(code)), or decode(code) without
+ * by_residual: every operation rounded once, no FMA contraction, so a numpy fp32
+ * expression gives the same bits.
+ *
+ * Search.  Per query the k rows of its probed lists that minimise sum (x_j -
+ * y_j)^2 (L2) or maximise sum x_j y_j (IP) over the decoded fp32 y, the sum in
+ * fp64 rounded once to fp32, ranked by (that value, list number, insertion order
+ * within the list); missing slots I = -1, D = +-FLT_MAX.  k <= 32: the fused path
+ * (operand preparation per (query, probe) pair, the int8 MFMA list scan, exact
+ * refine + certification, the exact list scan for uncertified queries, all
+ * decided on the device); 32 < k <= FX_MAX_K: the exact list scan (one fp64 pass
+ * over the decoded rows of the probed lists: correct, slow; the limitation of
+ * both parent sections as k nears 32 holds here too).
+ *
+ * Errors: those of fx_ivf_* and fx_sq_*, with the same limits.  FX_E_ARG also for
+ * training or set_trained while the quantizer does not hold nlist centroids or
+ * the index holds rows, and for add or search before the tables are trained.
+ *
+ * Out of scope: write_index / read_index (faiss's "IwSQ" layout cannot be checked
+ * here), remove_ids, range_search, selectors, reconstruct* by id, sharding, the
+ * search graph, the other qtypes, IndexIVFPQ. */
+typedef struct FxIvfSq FxIvfSq;
+int fx_ivfsq_create(FxIndex* quantizer, int d, int64_t nlist, int qtype, int metric, int by_residual, FxIvfSq** out);
+void fx_ivfsq_free(FxIvfSq* ivfsq);
+/* Assigns x [n][d] to lists, forms r, and feeds the min / max pass (bitwise
+ * reproducible).  more != 0: the call only accumulates and the index stays
+ * untrained; the call with more == 0 finishes (fx_sq_train's protocol). */
+int fx_ivfsq_train(FxIvfSq* ivfsq, int64_t n, const void* x, int x_dtype, int x_mem, int more);
+int fx_ivfsq_is_trained(const FxIvfSq* ivfsq, int* out);
+/* out / trained: host [2 d] floats, [vmin | vdiff]. */
+int fx_ivfsq_get_trained(FxIvfSq* ivfsq, float* out);
+int fx_ivfsq_set_trained(FxIvfSq* ivfsq, const float* trained);
+/* ids NULL: sequential ids ntotal .. ntotal + n - 1.  Device x (and ids) is
+ * stream-ordered; host x blocks. */
+int fx_ivfsq_add(FxIvfSq* ivfsq, int64_t n, const void* x, int x_dtype, int x_mem, const int64_t* ids, int ids_mem);
+/* Host results block; device queries and results are stream-ordered (the first
+ * search after an add synchronises once for the regroup). */
+int fx_ivfsq_search(FxIvfSq* ivfsq, int64_t nq, const void* q, int q_dtype, int q_mem, int k, int nprobe, float* D,
+                    int64_t* I, int out_mem);
+/* Empties the lists; the quantizer and the tables (both trainings) stay. */
+int fx_ivfsq_reset(FxIvfSq* ivfsq);
+int fx_ivfsq_ntotal(const FxIvfSq* ivfsq, int64_t* out);
+/* out: host [nlist]. */
+int fx_ivfsq_list_sizes(FxIvfSq* ivfsq, int64_t* out);
+/* *n = rows of `list`; out (host, cap entries; may be NULL with cap 0) receives
+ * the first min(*n, cap) ids / code rows in insertion order.  Codes are faiss's
+ * unsigned bytes [.][d]. */
+int fx_ivfsq_list_ids(FxIvfSq* ivfsq, int64_t list, int64_t* out, int64_t cap, int64_t* n);
+int fx_ivfsq_list_codes(FxIvfSq* ivfsq, int64_t list, uint8_t* out, int64_t cap, int64_t* n);
+int fx_ivfsq_set_stream(FxIvfSq* ivfsq, void* stream);
+/* As fx_ivf_last_counts / _last_plan / _profile / _profile_read (pairs_ms: the
+ * pair grouping and the per-pair operand preparation). */
+int fx_ivfsq_last_counts(FxIvfSq* ivfsq, int64_t* fallbacks, int64_t* exact_fallbacks, int64_t* dropped);
+int fx_ivfsq_last_plan(FxIvfSq* ivfsq, int* path, int* chunks, int* slots, int64_t* q_batch, int64_t* grid);
+int fx_ivfsq_profile(FxIvfSq* ivfsq, int enable);
+int fx_ivfsq_profile_read(FxIvfSq* ivfsq, double* coarse_ms, double* pairs_ms, double* scan_ms, double* refine_ms,
+                          int64_t* passes);
 
 /* faiss.write_index / faiss.read_index on the IxF2 format (faiss_store.py:
  * 91,106): fourcc "IxF2", i32 d, i64 ntotal, i64 1<<20, i64 1<<20,

@@ -116,6 +116,25 @@ SIGNATURES = {
                              ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "fx_sq_profile": (_i, [_vp, _i]),
     "fx_sq_profile_read": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(_i64)]),
+    "fx_ivfsq_create": (_i, [_vp, _i, _i64, _i, _i, _i, _pp]),
+    "fx_ivfsq_free": (None, [_vp]),
+    "fx_ivfsq_train": (_i, [_vp, _i64, _vp, _i, _i, _i]),
+    "fx_ivfsq_is_trained": (_i, [_vp, ctypes.POINTER(_i)]),
+    "fx_ivfsq_get_trained": (_i, [_vp, _vp]),
+    "fx_ivfsq_set_trained": (_i, [_vp, _vp]),
+    "fx_ivfsq_add": (_i, [_vp, _i64, _vp, _i, _i, _vp, _i]),
+    "fx_ivfsq_search": (_i, [_vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _i]),
+    "fx_ivfsq_reset": (_i, [_vp]),
+    "fx_ivfsq_ntotal": (_i, [_vp, ctypes.POINTER(_i64)]),
+    "fx_ivfsq_list_sizes": (_i, [_vp, _vp]),
+    "fx_ivfsq_list_ids": (_i, [_vp, _i64, _vp, _i64, ctypes.POINTER(_i64)]),
+    "fx_ivfsq_list_codes": (_i, [_vp, _i64, _vp, _i64, ctypes.POINTER(_i64)]),
+    "fx_ivfsq_set_stream": (_i, [_vp, _vp]),
+    "fx_ivfsq_last_counts": (_i, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "fx_ivfsq_last_plan": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64),
+                                ctypes.POINTER(_i64)]),
+    "fx_ivfsq_profile": (_i, [_vp, _i]),
+    "fx_ivfsq_profile_read": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(_i64)]),
     "fx_index_write": (_i, [_vp, ctypes.c_char_p]),
     "fx_index_read": (_i, [ctypes.c_char_p, _i, _i, _pp]),
     "fx_merge_shards": (_i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),

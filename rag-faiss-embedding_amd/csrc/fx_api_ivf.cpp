@@ -15,32 +15,6 @@ using namespace fx;
 
 namespace {
 
-// The quantizer's searches run on the payload's stream for the duration of a
-// call (the quantizer locked): both directions ordered on the device, as
-// fx_index_set_stream orders a switch.
-struct BorrowQuant {
-    FxIndex* q;
-    hipStream_t s, prev_user, prev;
-    std::unique_lock<std::mutex> lk;
-    BorrowQuant(FxIndex* quant, hipStream_t stream) : q(quant), s(stream), lk(quant->mu) {
-        prev_user = q->user_stream;
-        prev = q->stream();
-    }
-    hipError_t begin() {
-        hipError_t e = hipSuccess;
-        if (prev != s) {
-            e = hipEventRecord(q->switch_ev, prev);
-            if (e == hipSuccess) e = hipStreamWaitEvent(s, q->switch_ev, 0);
-        }
-        q->user_stream = s;
-        return e;
-    }
-    ~BorrowQuant() {
-        q->user_stream = prev_user;
-        if (prev != s && hipEventRecord(q->switch_ev, s) == hipSuccess) (void)hipStreamWaitEvent(prev, q->switch_ev, 0);
-    }
-};
-
 int ivf_trained(const FxIvf* v, const char* who) {
     if (v->quant->ntotal != v->nlist)
         return set_err(FX_E_ARG, "%s: the index is not trained (the quantizer holds %lld of %lld centroids)", who,

@@ -186,6 +186,7 @@ struct Options {
     int scan_dbg = 0;        // FX_SCAN_DBG: ablation switches of -DFX_ABLATION builds / key dump (32)
     std::string trace, stamps, cand, keys;  // FX_SCAN_TRACE / _STAMPS / _CAND / _KEYS dump paths
     std::string sq_cand, ivf_cand;  // FX_SQ_CAND / FX_IVF_CAND: the scan lists of fx_sq_search / fx_ivf_search, per pass
+    std::string ivfsq_cand;         // FX_IVFSQ_CAND: the scan lists and pair operands of fx_ivfsq_search, per pass
 #else
     static constexpr int force_fallback = 0, scan_dbg = 0;
 #endif
@@ -234,6 +235,7 @@ struct Options {
         str("FX_SCAN_KEYS", keys);
         str("FX_SQ_CAND", sq_cand);
         str("FX_IVF_CAND", ivf_cand);
+        str("FX_IVFSQ_CAND", ivfsq_cand);
 #endif
     }
     // option name -> its slot and accepted range [lo, hi] (allowed: a value
@@ -576,6 +578,32 @@ struct FxIvf {
     std::mutex mu;
 };
 
+// The quantizer's searches run on the borrowing index's stream for the duration
+// of a call (the quantizer locked): both directions ordered on the device, as
+// fx_index_set_stream orders a switch.
+struct BorrowQuant {
+    FxIndex* q;
+    hipStream_t s, prev_user, prev;
+    std::unique_lock<std::mutex> lk;
+    BorrowQuant(FxIndex* quant, hipStream_t stream) : q(quant), s(stream), lk(quant->mu) {
+        prev_user = q->user_stream;
+        prev = q->stream();
+    }
+    hipError_t begin() {
+        hipError_t e = hipSuccess;
+        if (prev != s) {
+            e = hipEventRecord(q->switch_ev, prev);
+            if (e == hipSuccess) e = hipStreamWaitEvent(s, q->switch_ev, 0);
+        }
+        q->user_stream = s;
+        return e;
+    }
+    ~BorrowQuant() {
+        q->user_stream = prev_user;
+        if (prev != s && hipEventRecord(q->switch_ev, s) == hipSuccess) (void)hipStreamWaitEvent(prev, q->switch_ev, 0);
+    }
+};
+
 // ---- fx_api_sq.cpp -------------------------------------------------------------
 
 // A scalar-quantizer index (include/fx_index.h, fx_sq.hip): 8-bit signed codes
@@ -603,6 +631,48 @@ struct FxSq {
     int64_t last_qbatch = 0, last_grid = 0;
     // profiling (fx_sq_profile): 4 events per pass -- start, after the query preparation, after the scan
     // (exact path: the exact scan), after refine + exact fallback
+    bool profile = false;
+    std::vector<hipEvent_t> ev;
+    std::mutex mu;
+    hipStream_t stream() const { return user_stream ? user_stream : own_stream; }
+};
+
+// ---- fx_api_ivfsq.cpp ----------------------------------------------------------
+
+// An inverted file over 8-bit codes (include/fx_index.h, fx_ivfsq.hip).  `quant` is the caller's
+// coarse quantizer (borrowed).  The payload is FxSq's rows (signed codes with a whole tile past the
+// last row, n_c) with FxIvf's list state: labels, row_list (the rows' lists; nlist: an assignment
+// outside the lists), in list order once `dirty` is false.  cent holds the quantizer's centroids
+// widened to fp32 as they were when the tables were trained (by_residual only).
+struct FxIvfSq {
+    FxIndex* quant = nullptr;
+    int d = 0, qtype = 0, metric = fx::L2, device = 0, row_bytes = 0, by_residual = 1;
+    int64_t nlist = 0, ntotal = 0, cap_rows = 0;
+    bool trained = false, train_open = false;
+    bool dirty = false, sequential = false;
+    int64_t max_list_rows = 0;
+    std::vector<int> h_off;
+    fx::DevArr<char> codes, codes_alt;
+    fx::DevArr<float> nc, nc_alt, tables, cent;
+    fx::DevArr<int64_t> labels, labels_alt;
+    fx::DevArr<int> row_list, row_list_alt, list_off, max_rows;
+    fx::DevArr<unsigned> words, mm;
+    fx::DevArr<unsigned long long> bad;  // [0] non-finite training values, [1] assignments outside [0, nlist)
+    hipStream_t own_stream = nullptr, user_stream = nullptr;
+    hipEvent_t switch_ev = nullptr;
+    fx::Options opt;  // (force_fallback and the dump path of the diagnostic build, read at creation)
+    // workspace of train / add / the accessors
+    fx::DevBuf in, assign, tlist, resid, rws, io;
+    // search workspace
+    fx::DevBuf qin, qf32, planes, sigma, peps, pshift, coarse_d, coarse_i, pkeys, psorted, seg, ngrp, gbase, ptemp,
+        cand_d, cand_i, flag, outD, outI;
+    fx::DevArr<int> cnt;  // [0] dropped candidate ids, [1] queries flagged, [2] coarse entries outside the lists
+    fx::PinArr<int> pin_cnt;
+    bool counts_pending = false;
+    int64_t last_fallbacks = 0, last_dropped = 0, last_bad_probe = 0;
+    int last_plan[3] = {0, 0, 0};  // path, chunks, slots
+    int64_t last_qbatch = 0, last_grid = 0;
+    // profiling: 5 events per pass, as FxIvf's
     bool profile = false;
     std::vector<hipEvent_t> ev;
     std::mutex mu;

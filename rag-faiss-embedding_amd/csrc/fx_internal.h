@@ -1,5 +1,5 @@
 // fx_internal.h -- shared between the HIP translation units (fx_kernels.hip,
-// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip, fx_kmeans.hip, fx_ivf.hip, fx_sq.hip) and the host C ABI
+// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip, fx_kmeans.hip, fx_ivf.hip, fx_sq.hip, fx_ivfsq.hip) and the host C ABI
 // (fx_index.cpp, fx_api_*.cpp, fx_plan.cpp; their own header: fx_host.h):
 // tiling constants, kernel parameter blocks, the launchers' prototypes and
 // their host-side helpers.  Not part of the public ABI (include/fx_index.h).
@@ -537,6 +537,8 @@ struct IvfExact {
     int64_t* I;
 };
 hipError_t launch_ivf_exact(int st_dt, int metric, const IvfExact& p, hipStream_t s);
+// k_ivf_merge alone: the per-query merge of cd / ci lists another exact scan wrote (fx_ivfsq.hip)
+hipError_t launch_ivf_merge(int metric, const IvfExact& p, hipStream_t s);
 // *bad += the entries of coarse[0, n) outside [0, nlist) (the exact path of a whole pass, which forms no pairs)
 hipError_t launch_ivf_count_bad(const int64_t* coarse, int64_t n, int64_t nlist, int* bad, hipStream_t s);
 // flag[0] = n, flag[1 + i] = i (the exact path of a whole pass)
@@ -660,6 +662,96 @@ struct SqExact {
     int64_t* I;
 };
 hipError_t launch_sq_exact(int metric, const SqExact& p, hipStream_t s);
+// inverted file over 8-bit codes (fx_ivfsq.hip): faiss's IndexIVFScalarQuantizer.  The payload is
+// the inverted file's (list order, list_off, row_list) with the scalar quantizer's rows (signed
+// codes, n_c); with by_residual a code encodes fl32(x - c_l) and the row decodes to fl32(c_l +
+// decode(code)).  cent is the fp32 centroids [nlist][d], or null without by_residual.
+// out[i][0..d) <- fl32(x[i] - cent[row_list[i]]) (a list number outside [0, nlist): x[i] itself)
+hipError_t launch_ivfsq_residual(const void* x, int x_dt, int64_t n, int d, const int* row_list, int64_t nlist,
+                                 const float* cent, float* out, hipStream_t s);
+// words[SQ_W_RHO] <- the rounding bound of a decoded row: launch_sq_consts' per-dimension term plus
+// u (max_l |c_lj| + max |decode_j|) for the addition of the centroid (cent null: launch_sq_consts)
+hipError_t launch_ivfsq_consts(const float* trained, int d, const float* cent, int64_t nlist, unsigned* words,
+                               hipStream_t s);
+// out[i][0..d) <- faiss's unsigned bytes of stored rows [r0, r0 + n)
+hipError_t launch_ivfsq_codes_u8(const char* codes, int row_bytes, int64_t r0, int64_t n, int d, uint8_t* out,
+                                 hipStream_t s);
+// Operand preparation per (query, probe) pair p = q * np + j (the list's centroid folded in):
+//   L2  z = x - c_l - m, w = z o s, |x - y|^2 = |z|^2 - 2 w.c' + n_c      shift |z|^2
+//   IP  w = x o s,                  x.y       = x.(c_l + m) + w.c'        shift -x.(c_l + m)
+// planes, sigma, shift (fp32: the scan adds it to the key) and the pair's bound E.
+struct IvfSqPrep {
+    const void* q;          // [nq][d] on the device
+    int q_dt, metric, d, row_bytes;
+    int64_t nq;
+    int np;
+    int64_t pairs_pad;      // >= nq * np; rows past nq * np are written as zero operands
+    const int64_t* coarse;  // [nq][np] probed lists
+    int64_t nlist;
+    const float* cent;      // [nlist][d] or null
+    const float* trained;
+    const unsigned* words;
+    float* qf32;            // [nq][row_bytes] fp32 queries, zero padded
+    char* planes;           // [SQ_P][pairs_pad][row_bytes]
+    float* sigma;           // [pairs_pad]
+    float* peps;            // [pairs_pad] E of the pair, the rounding of the shift and its addition included
+    float* pshift;          // [pairs_pad]
+    int* zero[2];           // counters set to 0
+};
+hipError_t launch_ivfsq_prep(const IvfSqPrep& p, hipStream_t s);
+// k_ivfsq_scan: k_ivf_scan's grid and list logic around k_sq_scan's int8 tile loop; the B planes
+// are fetched by pair number.  key = fl(fl(n_c - 2 sigma S) + shift) (IP: fl(-sigma S + shift)).
+struct IvfSqScan {
+    const char* codes;    // [rows][row_bytes] signed codes in list order, a whole tile past the end
+    const float* nc;
+    int row_bytes;
+    const int* list_off;
+    int64_t nlist;
+    const char* planes;   // [SQ_P][pairs_pad][row_bytes]
+    const float* sigma;   // [pairs_pad]
+    const float* pshift;  // [pairs_pad]
+    int64_t pairs_pad;
+    int np, C;
+    const uint64_t* sorted;
+    const int* seg;
+    const int* gbase;
+    float* cand_d;        // [nq][np * C][KP]
+    int* cand_i;
+    int64_t grid;
+};
+hipError_t launch_ivfsq_scan(int metric, const IvfSqScan& p, hipStream_t s);
+// k_sq_refine's three phases over [nq][slots][KP]; candidate keys carry their pair's shift, so the
+// certification runs with shift 0 and E = the largest of the query's pairs'
+struct IvfSqRefine {
+    const float* cand_d;
+    const int* cand_i;
+    int slots, np;
+    int64_t nq, ntotal;
+    int k, d, row_bytes;
+    const char* codes;
+    const int* row_list;    // [ntotal] the rows' lists
+    int64_t nlist;
+    const float* cent;      // or null
+    const float* trained;
+    const unsigned* words;
+    const float* qf32;      // [nq][row_bytes]
+    const float* peps;      // [nq * np]
+    const int64_t* labels;
+    float* D;
+    int64_t* I;
+    int* n_flag;
+    int* n_drop;
+    int force_fb;
+};
+hipError_t launch_ivfsq_refine(int metric, const IvfSqRefine& p, hipStream_t s);
+// k_ivfsq_exact (k_ivf_exact over decoded rows: decode plus centroid) + k_ivf_merge
+struct IvfSqExact {
+    IvfExact ex;            // codes: the signed codes; kdim: the fp32 queries' stride (row_bytes)
+    int d;
+    const float* trained;
+    const float* cent;      // or null
+};
+hipError_t launch_ivfsq_exact(int metric, const IvfSqExact& p, hipStream_t s);
 hipError_t launch_synth(void* out, int64_t row0, int64_t n, int d, int dtype, uint64_t seed,
                         hipStream_t s);
 hipError_t launch_to_f32(const void* codes, int st_dt, int row_bytes, int64_t n, int d, float* out,

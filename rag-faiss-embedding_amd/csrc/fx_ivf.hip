@@ -617,6 +617,11 @@ hipError_t launch_ivf_exact(int st_dt, int metric, const IvfExact& p, hipStream_
         return hipGetLastError();
     });
     if (e != hipSuccess) return e;
+    return launch_ivf_merge(metric, p, s);
+}
+
+hipError_t launch_ivf_merge(int metric, const IvfExact& p, hipStream_t s) {
+    if (p.k <= 0 || p.k > FX_BIG_K || p.np <= 0 || p.C <= 0 || !p.labels) return hipErrorInvalidValue;
     if (metric == L2) hipLaunchKernelGGL(k_ivf_merge<L2>, dim3(IVF_MERGE_GRID), dim3(BT_THREADS), 0, s, p);
     else hipLaunchKernelGGL(k_ivf_merge<IP>, dim3(IVF_MERGE_GRID), dim3(BT_THREADS), 0, s, p);
     return hipGetLastError();

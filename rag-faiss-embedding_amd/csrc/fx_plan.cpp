@@ -210,6 +210,28 @@ IvfPlan plan_ivf(int64_t nq, int nprobe_eff, int64_t nlist, int64_t max_list_row
     return P;
 }
 
+IvfSqPlan plan_ivfsq(int64_t nq, int nprobe_eff, int64_t nlist, int64_t max_list_rows, int64_t ntotal, int k,
+                     int row_bytes) {
+    IvfSqPlan P;
+    static_cast<IvfPlan&>(P) = plan_ivf(nq, nprobe_eff, nlist, max_list_rows, ntotal, k, row_bytes);
+    const int64_t np = std::max(1, nprobe_eff);
+    const int64_t rb = std::max(1, row_bytes);
+    const bool fused = P.path == IVF_PATH_FUSED;
+    const int64_t cand_q = (int64_t)P.slots * (fused ? KP : k) * 8;
+    if (fused) {
+        // a query costs its np operands and its lists; the padding of the pair count costs < 128 operands
+        const int64_t per_query = (int64_t)SQ_P * np * rb + cand_q;
+        const int64_t room = IVFSQ_PASS_BYTES - (int64_t)SQ_P * (TILE_Q - 1) * rb;
+        P.q_batch = std::max<int64_t>(1, std::min<int64_t>(P.q_batch, room / per_query));
+        const int64_t bp = P.q_batch * np;
+        P.grid = (bp / TILE_Q + std::min<int64_t>(nlist, bp)) * P.chunks;
+        P.pairs_pad = (bp + TILE_Q - 1) / TILE_Q * TILE_Q;
+        P.plane_bytes = (int64_t)SQ_P * P.pairs_pad * rb;
+    }
+    P.cand_bytes = P.q_batch * cand_q;
+    return P;
+}
+
 SqPlan plan_sq(int64_t nq, int64_t ntotal, int k, int row_bytes) {
     // row_bytes is part of the signature but does not enter today: a tile's cost does not change how
     // many workgroups fill the CUs

@@ -99,6 +99,20 @@ constexpr int64_t SQ_CAND_BYTES = 1ll << 30;
 // Exact: up to 64 splits of >= 1,024 rows, and the most queries whose [query][xsplit][k] lists fit.
 SqPlan plan_sq(int64_t nq, int64_t ntotal, int k, int row_bytes);
 
+// ---- inverted file over 8-bit codes (fx_ivfsq.hip): the plan of one IndexIVFScalarQuantizer search
+
+// plan_ivf's path, chunks, slots and grid; q_batch additionally keeps the pass's operand planes
+// (SQ_P * pairs_pad * row_bytes, one operand per (query, probe) pair) plus its candidate lists
+// within IVFSQ_PASS_BYTES.
+struct IvfSqPlan : IvfPlan {
+    int64_t pairs_pad = 0;    // roundup(q_batch * nprobe_eff, 128): plane rows of a full pass
+    int64_t plane_bytes = 0;  // SQ_P * pairs_pad * row_bytes (exact path: 0, it prepares no operand)
+    int64_t cand_bytes = 0;   // q_batch * slots * (KP or k) * 8
+};
+constexpr int64_t IVFSQ_PASS_BYTES = 1ll << 30;
+IvfSqPlan plan_ivfsq(int64_t nq, int nprobe_eff, int64_t nlist, int64_t max_list_rows, int64_t ntotal, int k,
+                     int row_bytes);
+
 // ---- remove_ids (fx_remove.hip): the host's chunk plan ----------------------
 
 // Kept rows before row r, for the rows the plan asks about: any row (the

@@ -30,7 +30,7 @@
 //                flagged queries and every search with KP < k <= FX_BIG_K:
 //                correct, but one fp64 pass over every row.
 //   k_sq_encode_u8 / k_sq_decode   the codec (sa_encode, sa_decode, reconstruct).
-#include "fx_device.h"
+#include "fx_sq_common.h"
 
 #include <algorithm>
 
@@ -40,12 +40,6 @@ namespace {
 
 constexpr int SQ_THREADS = 256;
 constexpr int SQ_GRID_CAP = 4096;
-// k_sq_scan's LDS: k_scan_topk's carve; its 64 KiB double buffer holds two
-// stages of (128 code rows + 3 x 128 plane rows) x 64 B
-constexpr int SQ_STAGE_BYTES = (TILE_R + SQ_P * TILE_Q) * SQ_STAGE_B;
-static_assert(2 * SQ_STAGE_BYTES == LDS_STAGE, "the int8 stages fill k_scan_topk's double buffer");
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 unsigned sq_grid(int64_t items, int per_block) {
     const int64_t g = (items + per_block - 1) / per_block;
@@ -53,34 +47,6 @@ unsigned sq_grid(int64_t items, int per_block) {
 }
 
 }  // namespace
-
-// the decoded value of signed code cs: two rounded fp32 operations on the
-// table value (c + 0.5) / 255, bitwise a numpy fp32 expression
-__device__ __forceinline__ float sq_decode1(int cs, float vmin, float vdiff) {
-    // contraction off, plain operators: each is one correctly rounded fp32 operation (hipcc's default
-    // fp32 division is correctly rounded), where the compiler would otherwise fuse the multiply into the add
-#pragma clang fp contract(off)
-    const float t = ((float)(cs + 128) + 0.5f) / 255.f;
-    const float p = t * vdiff;
-    return vmin + p;
-}
-// the unsigned code of x (each operation rounded once, no contraction)
-__device__ __forceinline__ int sq_encode1(float x, float vmin, float vdiff) {
-#pragma clang fp contract(off)
-    float xi = 0.f;
-    if (vdiff != 0.f) {
-        const float num = x - vmin;
-        xi = num / vdiff;
-        xi = xi > 0.f ? (xi < 1.f ? xi : 1.f) : 0.f;  // (NaN -> 0)
-    }
-    const float sc = 255.f * xi;
-    return (int)sc;
-}
-// y = m + s c' in exact arithmetic: the scale and the box centre of dimension j
-__device__ __forceinline__ void sq_affine(const float* __restrict__ trained, int d, int j, double& m, double& s) {
-    s = (double)trained[d + j] / 255.0;
-    m = (double)trained[j] + 128.5 * s;
-}
 
 // ---------------------------------------------------------------------------
 // training
@@ -246,16 +212,6 @@ __global__ __launch_bounds__(SQ_THREADS) void k_sq_decode(const char* __restrict
 // factor 2 of L2); fl(n_c) and the final addition cost u M^2 and u (M^2 + 2 A).
 // There is no accumulation term: the MFMA sums integers.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double sq_digit(double r) {
-    const double h = rint(r);
-    return h > 127.0 ? 127.0 : h < -127.0 ? -127.0 : h;
-}
-
 __global__ __launch_bounds__(SQ_THREADS) void k_sq_prep(SqPrep p) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -567,21 +523,6 @@ __device__ __forceinline__ double sq_exact_partial(const float* __restrict__ xq,
         }
     }
     return acc;
-}
-
-// k_refine's certification (fx_kernels.hip certified_v): every row the
-// selection dropped has scan key >= tb, so its exact distance D satisfies
-// D + 2 rho sqrt(D) >= T = tb + shift - E (rho = rho_dec for L2, 0 for IP)
-__device__ __forceinline__ bool sq_certified(float kth, float tb, double shift, float eps, double rho) {
-    const double T = (double)tb + shift - (double)eps;
-    double dmin = T;
-    if (rho > 0.0) {
-        const double t = T > 0.0 ? T : 0.0;
-        const double sd = t / (sqrt(rho * rho + t) + rho);
-        dmin = sd * sd * (1.0 - 1e-12);
-    }
-    const double kup = (double)kth + fabs((double)kth) * 2.384185791015625e-7;  // + 2 ulp
-    return kup < dmin;
 }
 
 // merge + exact refine + certification: one wave per query (k_refine's three

@@ -5,7 +5,7 @@ compiled under ``-DFX_DIAG`` (``make -C csrc diag``): its option table adds
 the test hooks the product library does not carry -- ``force_fallback``
 (1: every query through the device-gated re-scan, 2: through the exact fp64
 scan) and ``scan_dbg`` 32 (the scan's whole key matrix dumped to
-``FX_SCAN_KEYS``) -- plus the FX_SCAN_TRACE / _CAND dumps, and two dumps of
+``FX_SCAN_KEYS``) -- plus the FX_SCAN_TRACE / _CAND dumps, and three dumps of
 the newer scans' lists, written per pass before the refine reads them and the
 exact path writes over them (paths read when the index is created):
 
@@ -17,6 +17,11 @@ exact path writes over them (paths read when the index is created):
 ``FX_IVF_CAND``  fx_ivf_search: ``cand_d``, ``cand_i`` [nq][slots][KP], the
                  probed lists [nq][nprobe] i64, ``list_off`` [nlist + 1] i32
                  (tests/test_ivf_scan_parity.py)
+``FX_IVFSQ_CAND``  fx_ivfsq_search: ``cand_d``, ``cand_i`` [nq][slots][KP], the
+                 probed lists [nq][nprobe] i64, ``list_off`` [nlist + 1] i32, the
+                 pairs' ``sigma``, shift and ``E`` [pairs_pad] f32 each, the digit
+                 planes [3][pairs_pad][row_bytes] i8 and the rows' ``n_c``
+                 [ntotal] (tests/test_ivfsq_scan_parity.py)
 
 The classes here are the faiss.py ones with every call going to that build.
 """
@@ -52,6 +57,16 @@ class IndexIVFFlat(_faiss.IndexIVFFlat):
     """An inverted file lives in the build of its quantizer: this one takes a
     quantizer of this module.  ``FX_IVF_CAND`` comes from the environment when
     the index is created; ``force_fallback`` is the quantizer's option."""
+
+    def __init__(self, quantizer, *args, **kwargs):
+        assert quantizer._lib is lib, "the quantizer must be an index of the diagnostic build"
+        super().__init__(quantizer, *args, **kwargs)
+
+
+class IndexIVFScalarQuantizer(_faiss.IndexIVFScalarQuantizer):
+    """As ``IndexIVFFlat`` above: a quantizer of this module.  ``FX_IVFSQ_CAND``
+    and ``FX_FORCE_FALLBACK`` come from the environment when the index is
+    created."""
 
     def __init__(self, quantizer, *args, **kwargs):
         assert quantizer._lib is lib, "the quantizer must be an index of the diagnostic build"

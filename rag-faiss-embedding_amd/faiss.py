@@ -1137,8 +1137,13 @@ class IndexIVFFlat:
         self.verbose = False
         self._mode = None  # "seq" (add) or "ids" (add_with_ids) while the index holds rows
         self._h = ctypes.c_void_p()
-        self._check(self._lib.fx_ivf_create(quantizer._h, self._d, self.nlist, _DTYPES[dtype], self.metric_type,
-                                            ctypes.byref(self._h)))
+        self._check(self._fn("create")(quantizer._h, self._d, self.nlist, _DTYPES[dtype], self.metric_type,
+                                       ctypes.byref(self._h)))
+
+    _PFX = "fx_ivf_"  # the C entry points of this class (IndexIVFScalarQuantizer: its own set)
+
+    def _fn(self, name: str):
+        return getattr(self._lib, self._PFX + name)
 
     def _check(self, rc: int) -> None:
         check(rc, self._lib)
@@ -1150,7 +1155,7 @@ class IndexIVFFlat:
     @property
     def ntotal(self) -> int:
         v = ctypes.c_int64(0)
-        self._check(self._lib.fx_ivf_ntotal(self._h, ctypes.byref(v)))
+        self._check(self._fn("ntotal")(self._h, ctypes.byref(v)))
         return v.value
 
     @property
@@ -1161,7 +1166,7 @@ class IndexIVFFlat:
         s = _torch().cuda.current_stream(self.device).cuda_stream if use_torch else None
         if getattr(self, "_bound", _UNBOUND) == s:
             return
-        self._check(self._lib.fx_ivf_set_stream(self._h, ctypes.c_void_p(s) if s is not None else None))
+        self._check(self._fn("set_stream")(self._h, ctypes.c_void_p(s) if s is not None else None))
         self._bound = s
 
     def train(self, x) -> None:
@@ -1202,7 +1207,7 @@ class IndexIVFFlat:
             xptr, code, mem, n = x.ctypes.data_as(ctypes.c_void_p), _lib.F32, _lib.MEM_HOST, x.shape[0]
             self._bind_stream(dev_ids)
         assert n_ids is None or n_ids == n, f"add_with_ids: {n_ids} ids for {n} rows"
-        self._check(self._lib.fx_ivf_add(self._h, n, xptr, code, mem, iptr, imem))
+        self._check(self._fn("add")(self._h, n, xptr, code, mem, iptr, imem))
         if n > 0:
             self._mode = mode
 
@@ -1231,7 +1236,7 @@ class IndexIVFFlat:
         nprobe = self.nprobe
         if params is not None:
             if _selector_of(params) is not None:
-                raise NotImplementedError("IndexIVFFlat.search takes no selector")
+                raise NotImplementedError(f"{type(self).__name__}.search takes no selector")
             nprobe = getattr(params, "nprobe", nprobe)
         nprobe = int(nprobe)
         if nprobe < 1:
@@ -1257,7 +1262,7 @@ class IndexIVFFlat:
         nprobe = self._nprobe_of(params)
         assert self.is_trained, "the index is not trained"
         if k > _lib.MAX_K:
-            raise NotImplementedError(f"IndexIVFFlat.search: k = {k} above MAX_K = {_lib.MAX_K}")
+            raise NotImplementedError(f"{type(self).__name__}.search: k = {k} above MAX_K = {_lib.MAX_K}")
         if _is_device_tensor(x):
             t = _torch()
             assert x.dim() == 2 and x.shape[1] == self._d, "dimension mismatch"
@@ -1273,9 +1278,9 @@ class IndexIVFFlat:
                 assert a.dtype == dt and tuple(a.shape) == (nq, k) and a.is_contiguous(), \
                     f"{name} must be a contiguous {dt} tensor of shape ({nq}, {k})"
             self._bind_stream(True)
-            self._check(self._lib.fx_ivf_search(self._h, nq, ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x),
-                                                _lib.MEM_DEVICE, k, nprobe, ctypes.c_void_p(D.data_ptr()),
-                                                ctypes.c_void_p(I.data_ptr()), _lib.MEM_DEVICE))
+            self._check(self._fn("search")(self._h, nq, ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x),
+                                           _lib.MEM_DEVICE, k, nprobe, ctypes.c_void_p(D.data_ptr()),
+                                           ctypes.c_void_p(I.data_ptr()), _lib.MEM_DEVICE))
             return D, I
         x = np.ascontiguousarray(x, dtype=np.float32)
         assert x.ndim == 2 and x.shape[1] == self._d, "dimension mismatch"
@@ -1287,33 +1292,33 @@ class IndexIVFFlat:
                 a.flags.c_contiguous and a.flags.writeable, \
                 f"{name} must be a writeable C-contiguous {np.dtype(dt).name} array of shape ({nq}, {k})"
         self._bind_stream(False)
-        self._check(self._lib.fx_ivf_search(self._h, nq, x.ctypes.data, _lib.F32, _lib.MEM_HOST, k, nprobe,
-                                            Dh.ctypes.data, Ih.ctypes.data, _lib.MEM_HOST))
+        self._check(self._fn("search")(self._h, nq, x.ctypes.data, _lib.F32, _lib.MEM_HOST, k, nprobe,
+                                       Dh.ctypes.data, Ih.ctypes.data, _lib.MEM_HOST))
         return Dh, Ih
 
     def reset(self) -> None:
         """Empties the lists; the quantizer (the training) stays, as in faiss."""
-        self._check(self._lib.fx_ivf_reset(self._h))
+        self._check(self._fn("reset")(self._h))
         self._mode = None
 
     def list_sizes(self) -> np.ndarray:
         out = np.zeros(self.nlist, dtype=np.int64)
-        self._check(self._lib.fx_ivf_list_sizes(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        self._check(self._fn("list_sizes")(self._h, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
     def get_list_ids(self, l: int) -> np.ndarray:
         """The ids of list ``l`` in insertion order (numpy int64)."""
         n = ctypes.c_int64(0)
-        self._check(self._lib.fx_ivf_list_ids(self._h, int(l), None, 0, ctypes.byref(n)))
+        self._check(self._fn("list_ids")(self._h, int(l), None, 0, ctypes.byref(n)))
         out = np.empty(n.value, dtype=np.int64)
         if n.value:
-            self._check(self._lib.fx_ivf_list_ids(self._h, int(l), out.ctypes.data_as(ctypes.c_void_p), n.value,
-                                                  ctypes.byref(n)))
+            self._check(self._fn("list_ids")(self._h, int(l), out.ctypes.data_as(ctypes.c_void_p), n.value,
+                                             ctypes.byref(n)))
         return out
 
     def _counts(self):
         a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-        self._check(self._lib.fx_ivf_last_counts(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        self._check(self._fn("last_counts")(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
 
     def last_fallbacks(self) -> int:
@@ -1327,7 +1332,7 @@ class IndexIVFFlat:
 
     def profile(self, enable: bool = True) -> None:
         """Record HIP events around the parts of every search pass."""
-        self._check(self._lib.fx_ivf_profile(self._h, 1 if enable else 0))
+        self._check(self._fn("profile")(self._h, 1 if enable else 0))
 
     def profile_read(self) -> dict:
         """Milliseconds since the last read (waits for the stream): ``coarse``,
@@ -1335,7 +1340,7 @@ class IndexIVFFlat:
         (+ exact fallback), and the ``passes`` they cover."""
         ms = [ctypes.c_double(0) for _ in range(4)]
         n = ctypes.c_int64(0)
-        self._check(self._lib.fx_ivf_profile_read(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(n)))
+        self._check(self._fn("profile_read")(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(n)))
         return {"coarse": ms[0].value, "pairs": ms[1].value, "scan": ms[2].value, "refine": ms[3].value,
                 "passes": n.value}
 
@@ -1345,8 +1350,8 @@ class IndexIVFFlat:
         ``grid`` (the list scan's launch bound)."""
         p, c, s = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
         qb, g = ctypes.c_int64(0), ctypes.c_int64(0)
-        self._check(self._lib.fx_ivf_last_plan(self._h, ctypes.byref(p), ctypes.byref(c), ctypes.byref(s),
-                                               ctypes.byref(qb), ctypes.byref(g)))
+        self._check(self._fn("last_plan")(self._h, ctypes.byref(p), ctypes.byref(c), ctypes.byref(s),
+                                          ctypes.byref(qb), ctypes.byref(g)))
         return {"path": "exact" if p.value else "fused", "chunks": c.value, "slots": s.value, "q_batch": qb.value,
                 "grid": g.value}
 
@@ -1354,7 +1359,7 @@ class IndexIVFFlat:
         h = getattr(self, "_h", None)
         if h:
             try:
-                self._lib.fx_ivf_free(h)
+                self._fn("free")(h)
             except Exception:  # noqa: BLE001 - interpreter shutdown
                 pass
             self._h = None
@@ -1661,9 +1666,144 @@ class IndexScalarQuantizer:
             self._h = None
 
 
+# ---------------------------------------------------------------------------
+# faiss.IndexIVFScalarQuantizer (include/fx_index.h "inverted file over 8-bit codes")
+# ---------------------------------------------------------------------------
+class IndexIVFScalarQuantizer(IndexIVFFlat):
+    """``faiss.IndexIVFScalarQuantizer(quantizer, d, nlist, qtype, metric,
+    by_residual)`` with 8-bit codes: ``IndexIVFFlat``'s lists holding
+    ``IndexScalarQuantizer``'s rows, one byte per dimension.  With
+    ``by_residual`` (faiss's default) a row of list l is encoded as ``x -
+    c_l`` and decodes to ``c_l + decode(code)``, so the quantiser's box is the
+    size of a cluster, not of the corpus.  A search ranks the DECODED rows of
+    the probed lists exactly: ids bit-exact, distances the fp64 sum rounded
+    once, ranked by (distance, list number, insertion order within the list).
+
+    The definition restates faiss's from memory and is not checked against a
+    faiss build; in particular faiss ranks a row by the distance between the
+    query's residual and the decoded residual, this class by the decoded row.
+
+    ``train(x)`` trains the coarse quantizer as ``IndexIVFFlat.train`` does if
+    it is untrained, then the quantiser's tables on the residuals of ``x``.
+
+    Not offered: the other qtypes, selectors, ``remove_ids``,
+    ``range_search``, ``reconstruct*``, ``write_index`` / ``read_index``."""
+
+    _PFX = "fx_ivfsq_"
+
+    def __init__(self, quantizer, d: int, nlist: int, qtype: int = ScalarQuantizer.QT_8bit,
+                 metric: int = METRIC_L2, by_residual: bool = True, device: int = 0, niter: int = 10,
+                 seed: int = 1234):
+        qtype = int(qtype)
+        if qtype not in (ScalarQuantizer.QT_8bit, ScalarQuantizer.QT_8bit_uniform):
+            name = _QT_NAMES.get(qtype, f"qtype {qtype}")
+            raise NotImplementedError(f"IndexIVFScalarQuantizer: {name} is not offered (QT_8bit, QT_8bit_uniform)")
+        assert isinstance(quantizer, _FlatIndex), "quantizer must be an IndexFlatL2 / IndexFlatIP of this module"
+        assert quantizer.d == int(d), f"quantizer has d = {quantizer.d}, the index d = {int(d)}"
+        assert quantizer.device == int(device), f"quantizer on cuda:{quantizer.device}, index on cuda:{int(device)}"
+        assert metric in (METRIC_L2, METRIC_INNER_PRODUCT), "metric must be METRIC_L2 or METRIC_INNER_PRODUCT"
+        self.quantizer = quantizer
+        self._lib = quantizer._lib
+        self._d, self.nlist, self.metric_type = int(d), int(nlist), int(metric)
+        self.qtype, self.by_residual = qtype, bool(by_residual)
+        self.storage_dtype, self.device = "int8", int(device)
+        self.nprobe = 1
+        self.niter, self.seed = int(niter), int(seed)
+        self.verbose = False
+        self._mode = None
+        self._h = ctypes.c_void_p()
+        self._check(self._fn("create")(quantizer._h, self._d, self.nlist, qtype, self.metric_type,
+                                       1 if self.by_residual else 0, ctypes.byref(self._h)))
+
+    @property
+    def code_size(self) -> int:
+        return self._d
+
+    @property
+    def is_trained(self) -> bool:
+        if self.quantizer.ntotal != self.nlist:
+            return False
+        v = ctypes.c_int(0)
+        self._check(self._fn("is_trained")(self._h, ctypes.byref(v)))
+        return bool(v.value)
+
+    def _rows(self, x):
+        """(pointer, dtype code, mem, n, keep-alive) of row input ``x``."""
+        if _is_device_tensor(x):
+            assert x.dim() == 2 and x.shape[1] == self._d, "dimension mismatch"
+            assert x.device.index == self.device, f"tensor on cuda:{x.device.index}, index on cuda:{self.device}"
+            x = x.contiguous()
+            self._bind_stream(True)
+            return ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x), _lib.MEM_DEVICE, x.shape[0], x
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        assert x.ndim == 2 and x.shape[1] == self._d, "dimension mismatch"
+        self._bind_stream(False)
+        return x.ctypes.data_as(ctypes.c_void_p), _lib.F32, _lib.MEM_HOST, x.shape[0], x
+
+    def train(self, x) -> None:
+        """k-means on the quantizer if it holds no centroids yet (as
+        ``IndexIVFFlat.train``), then per-dimension (``QT_8bit_uniform``:
+        global) min and max of the residuals of ``x``: numpy rows, a device
+        tensor, or a flat index of this module (its stored rows, gathered on
+        the device chunk by chunk).  A no-op on a trained index, as faiss."""
+        if self.is_trained:
+            return
+        assert self.ntotal == 0, "train on an index that holds rows: reset() it first"
+        if self.quantizer.ntotal != self.nlist:
+            IndexIVFFlat.train(self, x)
+        if _is_index(x):
+            flat = _flat(x)
+            assert not flat.has_ids and flat.device == self.device and flat.d == self._d
+            t = _torch()
+            n = flat.ntotal
+            for r0 in range(0, n, KMEANS_CHUNK):
+                keys = t.arange(r0, min(n, r0 + KMEANS_CHUNK), dtype=t.int64, device=t.device("cuda", self.device))
+                ptr, code, mem, nr, _keep = self._rows(flat.reconstruct_batch(keys + flat._id_offset, dtype="storage"))
+                self._check(self._fn("train")(self._h, nr, ptr, code, mem, 1))
+            self._check(self._fn("train")(self._h, 0, None, _lib.F32, _lib.MEM_DEVICE, 0))
+            return
+        ptr, code, mem, n, _keep = self._rows(x)
+        self._check(self._fn("train")(self._h, n, ptr, code, mem, 0))
+
+    @property
+    def trained(self) -> np.ndarray:
+        """faiss's ``sq.trained``: ``[vmin[d] | vdiff[d]]`` fp32 (``QT_8bit_uniform``:
+        ``[vmin, vdiff]``), of the residuals with ``by_residual``."""
+        out = np.empty(2 * self._d, dtype=np.float32)
+        self._check(self._fn("get_trained")(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        if self.qtype == ScalarQuantizer.QT_8bit_uniform:
+            return np.array([out[0], out[self._d]], dtype=np.float32)
+        return out
+
+    def set_trained(self, arr) -> None:
+        """Install tables kept with numpy (the array ``trained`` returned); the
+        quantizer must hold its centroids already."""
+        assert self.ntotal == 0, "set_trained on an index that holds rows: reset() it first"
+        assert self.quantizer.ntotal == self.nlist, "the quantizer is not trained"
+        a = np.ascontiguousarray(arr, dtype=np.float32).reshape(-1)
+        if self.qtype == ScalarQuantizer.QT_8bit_uniform and a.size == 2:
+            a = np.concatenate([np.full(self._d, a[0], np.float32), np.full(self._d, a[1], np.float32)])
+        assert a.size == 2 * self._d, f"trained must hold {2 * self._d} floats"
+        self._check(self._fn("set_trained")(self._h, a.ctypes.data_as(ctypes.c_void_p)))
+
+    def get_list_codes(self, l: int) -> np.ndarray:
+        """The codes of list ``l`` in insertion order: faiss's unsigned bytes
+        ``(n, d)`` uint8."""
+        n = ctypes.c_int64(0)
+        self._check(self._fn("list_codes")(self._h, int(l), None, 0, ctypes.byref(n)))
+        out = np.empty((n.value, self._d), dtype=np.uint8)
+        if n.value:
+            self._check(self._fn("list_codes")(self._h, int(l), out.ctypes.data_as(ctypes.c_void_p), n.value,
+                                               ctypes.byref(n)))
+        return out
+
+
 def write_index(index, path: str) -> None:
     """``faiss.write_index`` (faiss_store.py:91): IxF2 file, fp32 codes; a
     labelled index (``IndexIDMap`` / ``IndexIDMap2``) as an IxM2 file."""
+    if isinstance(index, IndexIVFScalarQuantizer):
+        raise NotImplementedError("write_index of an IndexIVFScalarQuantizer: write its quantizer, keep `trained` "
+                                  "with numpy and re-add the rows")
     if isinstance(index, IndexIVFFlat):
         raise NotImplementedError("write_index of an IndexIVFFlat: write its quantizer and re-add the rows")
     if isinstance(index, IndexScalarQuantizer):

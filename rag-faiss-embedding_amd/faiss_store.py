@@ -32,7 +32,8 @@ class FAISSVectorStore:
 
     _instance = None
     _initialized = False
-    ivf = None  # the IndexIVFFlat over the store's rows (build_ivf); dropped by every call that changes the rows
+    ivf = None  # the IndexIVFFlat / IndexIVFScalarQuantizer over the store's rows (build_ivf); dropped by every
+                # call that changes the rows
     sq = None   # the IndexScalarQuantizer over the store's rows (build_sq); dropped by the same calls
 
     def __new__(cls, *args, **kwargs):
@@ -77,17 +78,25 @@ class FAISSVectorStore:
         rows = [r for r, doc in enumerate(self.doc_ids) if doc in allowed]
         return _fx.SearchParameters(sel=_fx.IDSelectorBatch(np.asarray(rows, dtype=np.int64)))
 
-    def build_ivf(self, nlist: int, nprobe: int = 8):
+    def build_ivf(self, nlist: int, nprobe: int = 8, qtype=None):
         """An ``IndexIVFFlat`` over the store's rows (extension): the coarse
         quantizer is trained on the store's own index, so the rows never leave
         the GPU, and the rows are added with ids equal to their row numbers, so
         ``doc_ids`` keeps mapping results.  Kept as ``self.ivf`` until a call
-        changes the rows; ``search(..., nprobe=n)`` uses it.  Errors are logged
-        and raised again, as in ``load_index``."""
+        changes the rows; ``search(..., nprobe=n)`` uses it.  With a ``qtype``
+        (``ScalarQuantizer.QT_8bit`` / ``QT_8bit_uniform``) the lists hold one
+        byte per dimension instead: an ``IndexIVFScalarQuantizer`` with
+        residual encoding, searched the same way (the k nearest DECODED rows
+        of the probed lists).  Errors are logged and raised again, as in
+        ``load_index``."""
         try:
             quantizer = _fx.IndexFlatL2(self.dimension, device=self.device)
-            ivf = _fx.IndexIVFFlat(quantizer, self.dimension, int(nlist), _fx.METRIC_L2, dtype=self.dtype,
-                                   device=self.device)
+            if qtype is None:
+                ivf = _fx.IndexIVFFlat(quantizer, self.dimension, int(nlist), _fx.METRIC_L2, dtype=self.dtype,
+                                       device=self.device)
+            else:
+                ivf = _fx.IndexIVFScalarQuantizer(quantizer, self.dimension, int(nlist), qtype, _fx.METRIC_L2,
+                                                  device=self.device)
             ivf.nprobe = int(nprobe)
             ivf.train(self.index)
             ivf.add_from_index(self.index)
