@@ -727,6 +727,89 @@ int fx_sq_last_plan(FxSq* sq, int* path, int* qtiles, int* splits, int* xsplits,
 int fx_sq_profile(FxSq* sq, int enable);
 int fx_sq_profile_read(FxSq* sq, double* prep_ms, double* scan_ms, double* refine_ms, int64_t* passes);
 
+/* ---- product quantizer: faiss IndexPQ (8-bit) ---------------------------------
+ *
+ *   faiss (Python)                      faiss C++ / C API                               this ABI
+ *   IndexPQ(d, M, nbits, metric)        faiss_IndexPQ_new_with_metric                   fx_pq_create
+ *   index.train(x)                      faiss_Index_train                               M k-means runs (the k-means calls
+ *                                                                                       above), then fx_pq_set_centroids
+ *   index.is_trained                    faiss_Index_is_trained                          fx_pq_is_trained
+ *   index.pq.centroids                  ProductQuantizer::centroids                     fx_pq_get_centroids / _set_centroids
+ *   index.add(x)                        faiss_Index_add                                 fx_pq_add
+ *   index.search(x, k)                  faiss_Index_search                              fx_pq_search
+ *   index.reset()                       faiss_Index_reset                               fx_pq_reset
+ *   index.ntotal                        faiss_Index_ntotal                              fx_pq_ntotal
+ *   index.reconstruct_n(i0, n)          faiss_Index_reconstruct_n                       fx_pq_reconstruct_n
+ *   index.reconstruct_batch(keys)       faiss_Index_reconstruct_batch                   fx_pq_reconstruct_batch
+ *   index.sa_encode(x) / sa_decode(c)   faiss_Index_sa_encode / faiss_Index_sa_decode   fx_pq_encode / fx_pq_decode
+ *   index.codes                         IndexPQ::codes                                  fx_pq_get_codes
+ *   (GC of the index)                   faiss_Index_free                                fx_pq_free
+ *
+ * This restates faiss's ProductQuantizer from memory; it is NOT checked against
+ * a faiss build (as the IxM2 note above).  d = M dsub; sub-quantizer m owns the
+ * dimensions [m dsub, (m + 1) dsub) and 256 fp32 centroids of dsub values;
+ * centroids is faiss's flat array [M][256][dsub].
+ *
+ *   encode:  code_m = argmin_j sum_e (x_{m dsub + e} - c_{m j e})^2, the sum in fp64 over e
+ *     ascending, every operation rounded once (no FMA contraction), the lowest j on a tie
+ *   decode:  y_{m dsub + e} = c_{m code_m e}  (a gather: bitwise)
+ *
+ * The index stores roundup(M, 16) code bytes and one fp32 constant (|decode|^2)
+ * per row; fx_pq_encode / _decode / _get_codes speak faiss's row-major [n][M]
+ * uint8.
+ *
+ * A search has the flat index's contract applied to the DECODED rows, exactly
+ * as the scalar quantizer's above: the k rows that minimise sum (x_j - y_j)^2
+ * (L2) or maximise sum x_j y_j (IP), the sum in fp64 rounded once to fp32,
+ * ranked by (that value, row); rows with equal codes tie exactly and rank by
+ * row.  k <= 32 and dsub % 8 == 0: the fused path (query preparation, the
+ * gather scan on the bf16 MFMA, exact refine + certification, the exact scan
+ * for uncertified queries).  32 < k <= FX_MAX_K, and every index whose dsub is
+ * no multiple of 8: the exact scan for the whole search, one fp64 pass over
+ * every decoded row per query -- correct but slow; fx_pq_last_plan reports it.
+ *
+ * Errors: FX_E_ARG for a null handle, a bad dtype / mem / metric, d % M != 0,
+ * add or search before the centroids are set, set_centroids on an index that
+ * holds rows, non-finite centroids, k < 1; FX_E_UNSUPPORTED for nbits != 8, k >
+ * FX_MAX_K and ntotal >= 2^31; FX_E_INTEGRITY as the scalar quantizer's.  nq ==
+ * 0 and n == 0 are FX_OK.
+ *
+ * Out of scope: IndexIVFPQ, nbits != 8, fast-scan 4-bit codes, OPQ, polysemous
+ * and symmetric (SDC) search, selectors, remove_ids, range_search, IndexIDMap
+ * over it, write_index / read_index, sharding and the search graph. */
+typedef struct FxPq FxPq;
+int fx_pq_create(int d, int M, int nbits, int metric, int device, FxPq** out);
+void fx_pq_free(FxPq* pq);
+int fx_pq_is_trained(const FxPq* pq, int* out);
+/* out / centroids: host [M][256][dsub] floats.  Setting them (an index without
+ * rows only) rebuilds the scan image and marks the index trained. */
+int fx_pq_get_centroids(FxPq* pq, float* out);
+int fx_pq_set_centroids(FxPq* pq, const float* centroids);
+/* Ids are the row numbers ntotal .. ntotal + n - 1.  Device x is stream-ordered;
+ * host x blocks. */
+int fx_pq_add(FxPq* pq, int64_t n, const void* x, int x_dtype, int x_mem);
+/* Host results block; device queries and results are stream-ordered. */
+int fx_pq_search(FxPq* pq, int64_t nq, const void* q, int q_dtype, int q_mem, int k, float* D, int64_t* I, int out_mem);
+/* Empties the index, keeps the centroids. */
+int fx_pq_reset(FxPq* pq);
+int fx_pq_ntotal(const FxPq* pq, int64_t* out);
+/* out [n][d] fp32 (out_mem) <- the decoded rows [i0, i0 + n) / the rows keys[i]
+ * (int64, keys_mem; a key outside [0, ntotal): a row of NaN, as the flat index). */
+int fx_pq_reconstruct_n(FxPq* pq, int64_t i0, int64_t n, float* out, int out_mem);
+int fx_pq_reconstruct_batch(FxPq* pq, int64_t n, const int64_t* keys, int keys_mem, float* out, int out_mem);
+/* sa_encode / sa_decode: x [n][d] (x_dtype) <-> codes [n][M], all three buffers
+ * in `mem`. */
+int fx_pq_encode(FxPq* pq, int64_t n, const void* x, int x_dtype, uint8_t* codes, int mem);
+int fx_pq_decode(FxPq* pq, int64_t n, const uint8_t* codes, float* out, int mem);
+/* out [n][M] (out_mem) <- the codes of the rows [i0, i0 + n). */
+int fx_pq_get_codes(FxPq* pq, int64_t i0, int64_t n, uint8_t* out, int out_mem);
+int fx_pq_set_stream(FxPq* pq, void* stream);
+/* As fx_sq_last_counts / fx_sq_last_plan / fx_sq_profile / fx_sq_profile_read. */
+int fx_pq_last_counts(FxPq* pq, int64_t* fallbacks, int64_t* exact_fallbacks, int64_t* dropped);
+int fx_pq_last_plan(FxPq* pq, int* path, int* qtiles, int* splits, int* xsplits, int64_t* q_batch, int64_t* grid);
+int fx_pq_profile(FxPq* pq, int enable);
+int fx_pq_profile_read(FxPq* pq, double* prep_ms, double* scan_ms, double* refine_ms, int64_t* passes);
+
 /* ---- inverted file over 8-bit codes: faiss IndexIVFScalarQuantizer ------------
  *
  *   faiss (Python)                               faiss C++ / C API                          this ABI

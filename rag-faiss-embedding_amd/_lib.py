@@ -116,6 +116,26 @@ SIGNATURES = {
                              ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "fx_sq_profile": (_i, [_vp, _i]),
     "fx_sq_profile_read": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(_i64)]),
+    "fx_pq_create": (_i, [_i, _i, _i, _i, _i, _pp]),
+    "fx_pq_free": (None, [_vp]),
+    "fx_pq_is_trained": (_i, [_vp, ctypes.POINTER(_i)]),
+    "fx_pq_get_centroids": (_i, [_vp, _vp]),
+    "fx_pq_set_centroids": (_i, [_vp, _vp]),
+    "fx_pq_add": (_i, [_vp, _i64, _vp, _i, _i]),
+    "fx_pq_search": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _vp, _i]),
+    "fx_pq_reset": (_i, [_vp]),
+    "fx_pq_ntotal": (_i, [_vp, ctypes.POINTER(_i64)]),
+    "fx_pq_reconstruct_n": (_i, [_vp, _i64, _i64, _vp, _i]),
+    "fx_pq_reconstruct_batch": (_i, [_vp, _i64, _vp, _i, _vp, _i]),
+    "fx_pq_encode": (_i, [_vp, _i64, _vp, _i, _vp, _i]),
+    "fx_pq_decode": (_i, [_vp, _i64, _vp, _vp, _i]),
+    "fx_pq_get_codes": (_i, [_vp, _i64, _i64, _vp, _i]),
+    "fx_pq_set_stream": (_i, [_vp, _vp]),
+    "fx_pq_last_counts": (_i, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "fx_pq_last_plan": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i),
+                             ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "fx_pq_profile": (_i, [_vp, _i]),
+    "fx_pq_profile_read": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(_i64)]),
     "fx_ivfsq_create": (_i, [_vp, _i, _i64, _i, _i, _i, _pp]),
     "fx_ivfsq_free": (None, [_vp]),
     "fx_ivfsq_train": (_i, [_vp, _i64, _vp, _i, _i, _i]),

@@ -187,6 +187,7 @@ struct Options {
     std::string trace, stamps, cand, keys;  // FX_SCAN_TRACE / _STAMPS / _CAND / _KEYS dump paths
     std::string sq_cand, ivf_cand;  // FX_SQ_CAND / FX_IVF_CAND: the scan lists of fx_sq_search / fx_ivf_search, per pass
     std::string ivfsq_cand;         // FX_IVFSQ_CAND: the scan lists and pair operands of fx_ivfsq_search, per pass
+    std::string pq_cand;            // FX_PQ_CAND: the scan lists, query operands and row constants of fx_pq_search, per pass
 #else
     static constexpr int force_fallback = 0, scan_dbg = 0;
 #endif
@@ -236,6 +237,7 @@ struct Options {
         str("FX_SQ_CAND", sq_cand);
         str("FX_IVF_CAND", ivf_cand);
         str("FX_IVFSQ_CAND", ivfsq_cand);
+        str("FX_PQ_CAND", pq_cand);
 #endif
     }
     // option name -> its slot and accepted range [lo, hi] (allowed: a value
@@ -631,6 +633,38 @@ struct FxSq {
     int64_t last_qbatch = 0, last_grid = 0;
     // profiling (fx_sq_profile): 4 events per pass -- start, after the query preparation, after the scan
     // (exact path: the exact scan), after refine + exact fallback
+    bool profile = false;
+    std::vector<hipEvent_t> ev;
+    std::mutex mu;
+    hipStream_t stream() const { return user_stream ? user_stream : own_stream; }
+};
+
+// ---- fx_api_pq.cpp -------------------------------------------------------------
+
+// A product quantizer index (include/fx_index.h "product quantizer", fx_pq.hip).  The fp32 centroids
+// are the truth; the scan image and the three constants of the bound are rebuilt from them on the
+// host whenever they are set.  Rows: stride = roundup(M, 16) code bytes and one fp32 n_y each.
+struct FxPq {
+    int d = 0, M = 0, dsub = 0, metric = fx::L2, device = 0, stride = 0, kp = 0;
+    int64_t ntotal = 0, cap_rows = 0;
+    bool trained = false;
+    std::vector<float> h_cb;     // [M][256][dsub], the host copy fx_pq_get_centroids returns
+    double Y = 0, Ry = 0, Yl = 0;  // max |decode|, max |y - y_hi - y_lo|, max |y_lo| over any code row
+    fx::DevArr<uint8_t> codes;
+    fx::DevArr<float> ny, cb;
+    fx::DevArr<char> img;        // dsub % 8 == 0: [hi | lo] bf16 planes of pq_plane_bytes each
+    hipStream_t own_stream = nullptr, user_stream = nullptr;
+    hipEvent_t switch_ev = nullptr;
+    fx::Options opt;  // (force_fallback and the dump path of the diagnostic build, read at creation)
+    // workspace of add / search / the codec
+    fx::DevBuf in, qf32, planes, eps, rho, shift, cand_d, cand_i, flag, outD, outI, io;
+    fx::DevArr<int> cnt;  // [0] dropped candidate ids, [1] queries flagged
+    fx::PinArr<int> pin_cnt;
+    bool counts_pending = false;
+    int64_t last_fallbacks = 0, last_dropped = 0;
+    int last_plan[4] = {0, 0, 0, 0};  // path, query tiles, splits, exact splits
+    int64_t last_qbatch = 0, last_grid = 0;
+    // profiling (fx_pq_profile): 4 events per pass, as FxSq's
     bool profile = false;
     std::vector<hipEvent_t> ev;
     std::mutex mu;

@@ -1,5 +1,5 @@
 // fx_internal.h -- shared between the HIP translation units (fx_kernels.hip,
-// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip, fx_kmeans.hip, fx_ivf.hip, fx_sq.hip, fx_ivfsq.hip) and the host C ABI
+// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip, fx_kmeans.hip, fx_ivf.hip, fx_sq.hip, fx_ivfsq.hip, fx_pq.hip) and the host C ABI
 // (fx_index.cpp, fx_api_*.cpp, fx_plan.cpp; their own header: fx_host.h):
 // tiling constants, kernel parameter blocks, the launchers' prototypes and
 // their host-side helpers.  Not part of the public ABI (include/fx_index.h).
@@ -752,6 +752,89 @@ struct IvfSqExact {
     const float* cent;      // or null
 };
 hipError_t launch_ivfsq_exact(int metric, const IvfSqExact& p, hipStream_t s);
+// product quantizer (fx_pq.hip): faiss's IndexPQ with 8-bit codes.  cb = the fp32 centroids
+// [M][256][dsub].  A stored row is pq_stride(M) = roundup(M, 16) code bytes (padding 0) plus ny[row]
+// = |decode|^2 (fp64 sum in dimension order, rounded once).  The scan image of the centroids (dsub %
+// 8 == 0 only) is two bf16 planes [hi | lo] of pq_plane_bytes each: plane[(m * 256 + j) * dsub + e],
+// then one 16-B piece of zeros, which the stage pieces past d gather.
+constexpr int PQ_KSUB = 256;
+constexpr int PQ_STAGE_D = 32;  // dimensions of each row staged per pipeline stage (64 B per plane: one MFMA k-chunk)
+constexpr int PQ_STAGE_BYTES = 2 * (TILE_R + TILE_Q) * PQ_STAGE_D * 2;  // [A hi | A lo | B hi | B lo]
+static_assert(2 * PQ_STAGE_BYTES == LDS_STAGE, "the gather stages fill k_scan_topk's double buffer");
+constexpr int PQ_EXACT_GRID = 1024, PQ_MERGE_GRID = 256;
+inline int pq_stride(int M) { return (M + 15) / 16 * 16; }
+inline int pq_kpad(int d) { return (d + PQ_STAGE_D - 1) / PQ_STAGE_D * PQ_STAGE_D; }
+inline int64_t pq_plane_bytes(int M, int dsub) { return ((int64_t)M * PQ_KSUB * dsub + 8) * 2; }
+// out[r * stride + m] <- argmin_j |x[r][m dsub ..] - cb[m][j]|^2 (fp64, dimensions ascending, every
+// operation rounded once, the lowest j on a tie); bytes m >= M of a row are not written
+hipError_t launch_pq_encode(const void* x, int x_dt, int64_t n, int d, int M, int dsub, const float* cb, uint8_t* out,
+                            int stride, hipStream_t s);
+hipError_t launch_pq_ny(const uint8_t* codes, int stride, int64_t n, int M, int dsub, const float* cb, float* ny,
+                        hipStream_t s);
+// out[i][0..d) fp32 <- the centroids of source row r_i of codes [nrows][stride] (keys null: r_i = key0 +
+// i).  A key outside [0, nrows): a row of all-ones bits (NaN), nothing read.
+hipError_t launch_pq_decode(const uint8_t* codes, int stride, int64_t nrows, const int64_t* keys, int64_t key0,
+                            int64_t n, int M, int dsub, const float* cb, float* out, hipStream_t s);
+struct PqPrep {
+    const void* q;        // [nq][d] on the device
+    int q_dt, metric, d, kp;
+    int64_t nq, nq_pad;
+    double Y, Ry, Yl;     // index constants: max |decode|, max |y - y_hi - y_lo|, max |y_lo| over any code row
+    float* qf32;          // [nq_pad][kp] fp32 queries, zero padded
+    uint16_t* planes;     // [2][nq_pad][kp] bf16 hi / lo of -2 x (IP: -x)
+    float* qeps;          // [nq] E
+    float* qrho;          // [nq] |x' - x'_hi - x'_lo| (reported; the bound uses it inside E)
+    double* qshift;       // [nq] |x|^2 (L2), 0 (IP)
+    int* zero[2];         // counters set to 0
+};
+hipError_t launch_pq_prep(const PqPrep& p, hipStream_t s);
+struct PqScan {
+    const uint8_t* codes; // [cap_rows][stride], a whole tile past the last row, padding rows code 0
+    const float* ny;
+    int64_t ntotal;
+    int stride, M, dsub, d, kp;
+    const char* img;      // the scan image
+    int64_t plane_bytes;
+    const uint16_t* planes;
+    int64_t nq, nq_pad;
+    int n_qtiles, n_ctiles, splits;
+    float* cand_d;        // [n_qtiles][splits][TILE_Q][KP]
+    int* cand_i;
+};
+hipError_t launch_pq_scan(int metric, const PqScan& p, hipStream_t s);
+struct PqRefine {
+    const float* cand_d;
+    const int* cand_i;
+    int splits;
+    int64_t nq, ntotal;
+    int k, d, kp, M, dsub, stride;
+    const uint8_t* codes;
+    const float* cb;
+    const float* qf32;
+    const float* qeps;
+    const double* qshift;
+    float* D;
+    int64_t* I;
+    int* n_flag;          // [0] count, [1 ..] flagged queries
+    int* n_drop;
+    int force_fb;
+};
+hipError_t launch_pq_refine(int metric, const PqRefine& p, hipStream_t s);
+// k_pq_exact + k_pq_merge for the queries n_flag[1 ..] (count n_flag[0], read on the device)
+struct PqExact {
+    const uint8_t* codes;
+    int stride, M, dsub, d, kp;
+    int64_t ntotal;
+    const float* cb;
+    const float* qf32;
+    const int* n_flag;
+    int k, xs;
+    float* cd;
+    int* ci;
+    float* D;
+    int64_t* I;
+};
+hipError_t launch_pq_exact(int metric, const PqExact& p, hipStream_t s);
 hipError_t launch_synth(void* out, int64_t row0, int64_t n, int d, int dtype, uint64_t seed,
                         hipStream_t s);
 hipError_t launch_to_f32(const void* codes, int st_dt, int row_bytes, int64_t n, int d, float* out,

@@ -232,6 +232,20 @@ IvfSqPlan plan_ivfsq(int64_t nq, int nprobe_eff, int64_t nlist, int64_t max_list
     return P;
 }
 
+// the exact scan for a whole search: xs corpus splits per query, the most queries whose [query][xsplit][k]
+// lists fit SQ_CAND_BYTES
+static SqPlan sq_exact_plan(int64_t nq, int xs, int k) {
+    SqPlan P;
+    P.path = SQ_PATH_EXACT;
+    P.xsplits = xs;
+    P.splits = 1;
+    P.q_batch = std::max<int64_t>(1, std::min<int64_t>(nq, SQ_CAND_BYTES / ((int64_t)xs * k * 8)));
+    P.qtiles = (int)((P.q_batch + TILE_Q - 1) / TILE_Q);
+    P.grid = SQ_EXACT_GRID;
+    P.cand_bytes = P.q_batch * xs * k * 8;
+    return P;
+}
+
 SqPlan plan_sq(int64_t nq, int64_t ntotal, int k, int row_bytes) {
     // row_bytes is part of the signature but does not enter today: a tile's cost does not change how
     // many workgroups fill the CUs
@@ -241,15 +255,7 @@ SqPlan plan_sq(int64_t nq, int64_t ntotal, int k, int row_bytes) {
     nq = std::max<int64_t>(nq, 1);
     const int nct = (int)std::max<int64_t>(1, (ntotal + TILE_R - 1) / TILE_R);
     const int xs = (int)std::max<int64_t>(1, std::min<int64_t>(64, ntotal / 1024));
-    if (P.path == SQ_PATH_EXACT) {
-        P.xsplits = xs;
-        P.splits = 1;
-        P.q_batch = std::max<int64_t>(1, std::min<int64_t>(nq, SQ_CAND_BYTES / ((int64_t)xs * k * 8)));
-        P.qtiles = (int)((P.q_batch + TILE_Q - 1) / TILE_Q);
-        P.grid = SQ_EXACT_GRID;
-        P.cand_bytes = P.q_batch * xs * k * 8;
-        return P;
-    }
+    if (P.path == SQ_PATH_EXACT) return sq_exact_plan(nq, xs, k);
     constexpr int min_tiles = 3;
     const int64_t per_list = (int64_t)TILE_Q * KP * 8;
     int64_t qb = nq;
@@ -266,6 +272,14 @@ SqPlan plan_sq(int64_t nq, int64_t ntotal, int k, int row_bytes) {
     P.xsplits = std::min(P.splits, xs);
     P.grid = (int64_t)P.qtiles * P.splits;
     return P;
+}
+
+SqPlan plan_pq(int64_t nq, int64_t ntotal, int k, int M, int dsub) {
+    // M does not enter: a tile's cost does not change how many workgroups fill the CUs
+    (void)M;
+    if (dsub % 8 == 0) return plan_sq(nq, ntotal, k, 0);
+    const int xs = (int)std::max<int64_t>(1, std::min<int64_t>(64, ntotal / 1024));
+    return sq_exact_plan(std::max<int64_t>(nq, 1), xs, k);
 }
 
 bool plan_remove(const KeptPrefix& P, int64_t stage_rows, std::vector<RemoveChunk>& out) {

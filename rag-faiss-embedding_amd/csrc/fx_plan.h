@@ -99,6 +99,12 @@ constexpr int64_t SQ_CAND_BYTES = 1ll << 30;
 // Exact: up to 64 splits of >= 1,024 rows, and the most queries whose [query][xsplit][k] lists fit.
 SqPlan plan_sq(int64_t nq, int64_t ntotal, int k, int row_bytes);
 
+// ---- product quantizer (fx_pq.hip): the plan of one IndexPQ search
+
+// plan_sq's plan with one more reason for the exact path: the fused gather scan stages 16-B pieces of
+// a centroid, so it needs dsub % 8 == 0; any other dsub takes the exact scan (k_pq_exact) at every k.
+SqPlan plan_pq(int64_t nq, int64_t ntotal, int k, int M, int dsub);
+
 // ---- inverted file over 8-bit codes (fx_ivfsq.hip): the plan of one IndexIVFScalarQuantizer search
 
 // plan_ivf's path, chunks, slots and grid; q_batch additionally keeps the pass's operand planes

@@ -1,4 +1,5 @@
-// fx_sq_common.h -- device helpers the two 8-bit indexes share (fx_sq.hip, fx_ivfsq.hip): the
+// fx_sq_common.h -- device helpers the two 8-bit indexes share (fx_sq.hip, fx_ivfsq.hip; fx_pq.hip
+// takes the certification test): the
 // codec's scalar encode / decode, the affine form of a table entry, the digit of a query
 // operand plane, the refine's certification test, and the stage layout of the int8 tile loop.
 #pragma once

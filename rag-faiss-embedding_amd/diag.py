@@ -22,6 +22,10 @@ exact path writes over them (paths read when the index is created):
                  pairs' ``sigma``, shift and ``E`` [pairs_pad] f32 each, the digit
                  planes [3][pairs_pad][row_bytes] i8 and the rows' ``n_c``
                  [ntotal] (tests/test_ivfsq_scan_parity.py)
+``FX_PQ_CAND``   fx_pq_search: ``cand_d``, ``cand_i`` [qtiles][splits][128][KP],
+                 ``E`` [nq], the shift [nq] f64, the query planes [2][nq_pad][kp]
+                 bf16 ([hi | lo]), the rows' codes [ntotal][roundup(M, 16)] u8 and
+                 ``n_y`` [ntotal] (tests/test_pq_scan_parity.py)
 
 The classes here are the faiss.py ones with every call going to that build.
 """
@@ -49,6 +53,13 @@ class IndexFlatIP(_faiss.IndexFlatIP):
 class IndexScalarQuantizer(_faiss.IndexScalarQuantizer):
     """``force_fallback`` comes from ``FX_FORCE_FALLBACK`` in the environment
     when the index is created (it has no option table of its own)."""
+
+    _lib = lib
+
+
+class IndexPQ(_faiss.IndexPQ):
+    """``FX_PQ_CAND`` and ``FX_FORCE_FALLBACK`` come from the environment when
+    the index is created."""
 
     _lib = lib
 

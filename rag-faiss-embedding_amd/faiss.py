@@ -1667,6 +1667,325 @@ class IndexScalarQuantizer:
 
 
 # ---------------------------------------------------------------------------
+# faiss.IndexPQ (include/fx_index.h "product quantizer")
+# ---------------------------------------------------------------------------
+class ProductQuantizer:
+    """faiss's ``index.pq``: the shape of the quantizer (``M`` sub-quantizers of
+    ``dsub`` dimensions, ``ksub`` = 256 centroids each, ``code_size`` = M bytes)
+    and its ``centroids``, faiss's flat ``M * ksub * dsub`` fp32 array (get and
+    set; setting them installs the training).  ``niter`` and ``seed`` are the
+    k-means parameters ``IndexPQ.train`` uses."""
+
+    def __init__(self, index, d: int, M: int, nbits: int, niter: int, seed: int):
+        self._index = index
+        self.d, self.M, self.nbits = int(d), int(M), int(nbits)
+        self.dsub, self.ksub = self.d // self.M, 1 << self.nbits
+        self.code_size = self.M
+        self.niter, self.seed = int(niter), int(seed)
+
+    @property
+    def centroids(self) -> np.ndarray:
+        ix = self._index
+        out = np.empty(self.M * self.ksub * self.dsub, dtype=np.float32)
+        ix._check(ix._lib.fx_pq_get_centroids(ix._h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    @centroids.setter
+    def centroids(self, arr) -> None:
+        ix = self._index
+        a = np.ascontiguousarray(arr, dtype=np.float32).reshape(-1)
+        assert a.size == self.M * self.ksub * self.dsub, f"centroids must hold {self.M * self.ksub * self.dsub} floats"
+        assert ix.ntotal == 0, "centroids set on an index that holds rows: reset() it first"
+        ix._check(ix._lib.fx_pq_set_centroids(ix._h, a.ctypes.data_as(ctypes.c_void_p)))
+
+
+class IndexPQ:
+    """``faiss.IndexPQ(d, M, nbits, metric)`` with 8-bit codes: M bytes per row,
+    byte m naming one of the 256 centroids of sub-quantizer m; a row decodes to
+    the concatenation of its centroids (``reconstruct``, bitwise).  A search
+    ranks the DECODED vectors exactly as the flat index ranks its rows: ids
+    bit-exact, distances the fp64 sum rounded once, ties (rows with equal
+    codes) to the smaller row; ids are row numbers in insertion order.  The
+    definition restates faiss's from memory and is not checked against a faiss
+    build.
+
+    Not offered: ``nbits != 8`` (``NotImplementedError``), selectors,
+    ``remove_ids``, ``range_search``, ``IndexIDMap`` over it, ``write_index`` /
+    ``read_index``."""
+
+    _lib = lib
+
+    def __init__(self, d: int, M: int, nbits: int = 8, metric: int = METRIC_L2, device: int = 0, niter: int = 25,
+                 seed: int = 1234):
+        d, M, nbits = int(d), int(M), int(nbits)
+        if nbits != 8:
+            raise NotImplementedError(f"IndexPQ: nbits = {nbits} is not offered (8)")
+        if d <= 0 or M <= 0 or d % M != 0:
+            raise ValueError(f"IndexPQ: d = {d} is not a multiple of M = {M}")
+        assert metric in (METRIC_L2, METRIC_INNER_PRODUCT), "metric must be METRIC_L2 or METRIC_INNER_PRODUCT"
+        self._d, self.metric_type, self.device = d, int(metric), int(device)
+        self.pq = ProductQuantizer(self, d, M, nbits, niter, seed)
+        self._lib = self._lib  # the build this handle belongs to, for its whole life
+        self._h = ctypes.c_void_p()
+        self._check(self._lib.fx_pq_create(d, M, nbits, self.metric_type, self.device, ctypes.byref(self._h)))
+
+    def _check(self, rc: int) -> None:
+        check(rc, self._lib)
+
+    @property
+    def d(self) -> int:
+        return self._d
+
+    @property
+    def code_size(self) -> int:
+        return self.pq.M
+
+    @property
+    def ntotal(self) -> int:
+        v = ctypes.c_int64(0)
+        self._check(self._lib.fx_pq_ntotal(self._h, ctypes.byref(v)))
+        return v.value
+
+    @property
+    def is_trained(self) -> bool:
+        v = ctypes.c_int(0)
+        self._check(self._lib.fx_pq_is_trained(self._h, ctypes.byref(v)))
+        return bool(v.value)
+
+    def _bind_stream(self, use_torch: bool) -> None:
+        s = _torch().cuda.current_stream(self.device).cuda_stream if use_torch else None
+        if getattr(self, "_bound", _UNBOUND) == s:
+            return
+        self._check(self._lib.fx_pq_set_stream(self._h, ctypes.c_void_p(s) if s is not None else None))
+        self._bound = s
+
+    _rows = IndexScalarQuantizer._rows
+    _chunks_of = IndexScalarQuantizer._chunks_of
+
+    def train(self, x) -> None:
+        """``Kmeans(dsub, 256, niter=pq.niter, seed=pq.seed)`` on the contiguous
+        slice ``x[:, m * dsub:(m + 1) * dsub]`` of every sub-quantizer m, the
+        centroids then installed as ``pq.centroids``.  ``x``: numpy rows, a
+        device tensor, or a flat index of this module (its stored rows,
+        gathered on the device chunk by chunk).  Fewer than 256 rows is an
+        error."""
+        assert self.ntotal == 0, "train on an index that holds rows: reset() it first"
+        pq = self.pq
+        if _is_index(x):
+            t = _torch()
+            chunks = list(self._chunks_of(x))
+            n = sum(int(c.shape[0]) for c in chunks)
+
+            def piece(m):
+                return t.cat([c[:, m * pq.dsub:(m + 1) * pq.dsub] for c in chunks]).contiguous()
+        elif _is_device_tensor(x):
+            assert x.dim() == 2 and x.shape[1] == self._d, "dimension mismatch"
+            n = int(x.shape[0])
+
+            def piece(m):
+                return x[:, m * pq.dsub:(m + 1) * pq.dsub].contiguous()
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+            assert x.ndim == 2 and x.shape[1] == self._d, "dimension mismatch"
+            n = int(x.shape[0])
+
+            def piece(m):
+                return np.ascontiguousarray(x[:, m * pq.dsub:(m + 1) * pq.dsub])
+        if n < pq.ksub:
+            raise RuntimeError(f"IndexPQ.train: {n} training rows, fewer than the {pq.ksub} centroids of a sub-quantizer")
+        cents = np.empty((pq.M, pq.ksub, pq.dsub), dtype=np.float32)
+        for m in range(pq.M):
+            km = Kmeans(pq.dsub, pq.ksub, niter=pq.niter, seed=pq.seed, device=self.device)
+            km.train(piece(m))
+            cents[m] = km.centroids
+        pq.centroids = cents
+
+    def add(self, x) -> None:
+        """Encode and append the rows of ``x`` with ids ``ntotal .. ntotal + n - 1``."""
+        assert self.is_trained, "the index is not trained"
+        ptr, code, mem, n, _keep = self._rows(x)
+        self._check(self._lib.fx_pq_add(self._h, n, ptr, code, mem))
+
+    def add_from_index(self, index) -> None:
+        """Encode and append the stored rows of an unlabelled flat index of this
+        module in their order, gathered chunk by chunk on the device."""
+        for rows in self._chunks_of(index):
+            self.add(rows)
+
+    def search(self, x, k: int, *, params=None, D=None, I=None) -> Tuple:
+        """The k nearest decoded rows of every query.  numpy in -> numpy out
+        (blocks); device tensors in -> device tensors out, stream-ordered.
+        ``k <= 32`` with ``dsub % 8 == 0`` takes the fused path (the gather scan
+        on the bf16 MFMA + exact refine), anything else the exact scan (correct,
+        one fp64 pass over every row); ``k > MAX_K``: NotImplementedError."""
+        k = int(k)
+        if k <= 0:
+            raise AssertionError("k must be positive")
+        if params is not None and _selector_of(params) is not None:
+            raise NotImplementedError("IndexPQ.search takes no selector")
+        assert self.is_trained, "the index is not trained"
+        if k > _lib.MAX_K:
+            raise NotImplementedError(f"IndexPQ.search: k = {k} above MAX_K = {_lib.MAX_K}")
+        if _is_device_tensor(x):
+            t = _torch()
+            ptr, code, mem, nq, _keep = self._rows(x)
+            if D is None:
+                D = t.empty((nq, k), dtype=t.float32, device=x.device)
+            if I is None:
+                I = t.empty((nq, k), dtype=t.int64, device=x.device)
+            for name, a, dt in (("D", D, t.float32), ("I", I, t.int64)):
+                assert _is_device_tensor(a) and a.device == x.device, f"{name} must be on {x.device}"
+                assert a.dtype == dt and tuple(a.shape) == (nq, k) and a.is_contiguous(), \
+                    f"{name} must be a contiguous {dt} tensor of shape ({nq}, {k})"
+            self._check(self._lib.fx_pq_search(self._h, nq, ptr, code, mem, k, ctypes.c_void_p(D.data_ptr()),
+                                               ctypes.c_void_p(I.data_ptr()), _lib.MEM_DEVICE))
+            return D, I
+        ptr, code, mem, nq, _keep = self._rows(x)
+        Dh = np.empty((nq, k), dtype=np.float32) if D is None else D
+        Ih = np.empty((nq, k), dtype=np.int64) if I is None else I
+        for name, a, dt in (("D", Dh, np.float32), ("I", Ih, np.int64)):
+            assert isinstance(a, np.ndarray) and a.dtype == dt and a.shape == (nq, k) and \
+                a.flags.c_contiguous and a.flags.writeable, \
+                f"{name} must be a writeable C-contiguous {np.dtype(dt).name} array of shape ({nq}, {k})"
+        self._check(self._lib.fx_pq_search(self._h, nq, ptr, code, mem, k, Dh.ctypes.data, Ih.ctypes.data,
+                                           _lib.MEM_HOST))
+        return Dh, Ih
+
+    def reconstruct_n(self, i0: int = 0, n: int = -1) -> np.ndarray:
+        """The decoded rows ``[i0, i0 + n)`` as numpy fp32 (n = -1: to the end)."""
+        i0 = int(i0)
+        n = self.ntotal - i0 if int(n) < 0 else int(n)
+        out = np.empty((n, self._d), dtype=np.float32)
+        self._bind_stream(False)
+        self._check(self._lib.fx_pq_reconstruct_n(self._h, i0, n, out.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST))
+        return out
+
+    def reconstruct_batch(self, keys):
+        """The decoded rows of ``keys``: numpy in -> numpy fp32 out (a key
+        outside the index raises); an int64 device tensor in -> a device tensor
+        out, stream-ordered (a key outside the index gives a NaN row)."""
+        if _is_device_tensor(keys):
+            t = _torch()
+            keys = keys.to(t.int64).contiguous().reshape(-1)
+            out = t.empty((int(keys.numel()), self._d), dtype=t.float32, device=keys.device)
+            self._bind_stream(True)
+            self._check(self._lib.fx_pq_reconstruct_batch(self._h, int(keys.numel()), ctypes.c_void_p(keys.data_ptr()),
+                                                          _lib.MEM_DEVICE, ctypes.c_void_p(out.data_ptr()),
+                                                          _lib.MEM_DEVICE))
+            return out
+        keys = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        n = self.ntotal
+        if keys.size and (keys.min() < 0 or keys.max() >= n):
+            raise RuntimeError(f"reconstruct_batch: a key outside [0, {n})")
+        out = np.empty((int(keys.size), self._d), dtype=np.float32)
+        self._bind_stream(False)
+        self._check(self._lib.fx_pq_reconstruct_batch(self._h, int(keys.size), ctypes.c_void_p(keys.ctypes.data),
+                                                      _lib.MEM_HOST, ctypes.c_void_p(out.ctypes.data), _lib.MEM_HOST))
+        return out
+
+    def reconstruct(self, key: int) -> np.ndarray:
+        return self.reconstruct_batch(np.array([int(key)], dtype=np.int64))[0]
+
+    def sa_encode(self, x):
+        """Rows -> codes ``(n, M)`` uint8 (numpy in -> numpy out; a device
+        tensor in -> a device tensor out)."""
+        ptr, code, mem, n, _keep = self._rows(x)
+        M = self.pq.M
+        if mem == _lib.MEM_DEVICE:
+            t = _torch()
+            out = t.empty((n, M), dtype=t.uint8, device=_keep.device)
+            self._check(self._lib.fx_pq_encode(self._h, n, ptr, code, ctypes.c_void_p(out.data_ptr()), mem))
+            return out
+        out = np.empty((n, M), dtype=np.uint8)
+        self._check(self._lib.fx_pq_encode(self._h, n, ptr, code, ctypes.c_void_p(out.ctypes.data), mem))
+        return out
+
+    def sa_decode(self, codes):
+        """Codes ``(n, M)`` uint8 -> fp32 rows."""
+        M = self.pq.M
+        if _is_device_tensor(codes):
+            t = _torch()
+            assert codes.dtype == t.uint8 and codes.dim() == 2 and codes.shape[1] == M, "codes must be (n, M) uint8"
+            codes = codes.contiguous()
+            out = t.empty((codes.shape[0], self._d), dtype=t.float32, device=codes.device)
+            self._bind_stream(True)
+            self._check(self._lib.fx_pq_decode(self._h, codes.shape[0], ctypes.c_void_p(codes.data_ptr()),
+                                               ctypes.c_void_p(out.data_ptr()), _lib.MEM_DEVICE))
+            return out
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        assert codes.ndim == 2 and codes.shape[1] == M, "codes must be (n, M) uint8"
+        out = np.empty((codes.shape[0], self._d), dtype=np.float32)
+        self._bind_stream(False)
+        self._check(self._lib.fx_pq_decode(self._h, codes.shape[0], ctypes.c_void_p(codes.ctypes.data),
+                                           ctypes.c_void_p(out.ctypes.data), _lib.MEM_HOST))
+        return out
+
+    def get_codes(self, i0: int = 0, n: int = -1) -> np.ndarray:
+        """The codes of the rows ``[i0, i0 + n)`` as numpy ``(n, M)`` uint8 (n = -1: to the end)."""
+        i0 = int(i0)
+        n = self.ntotal - i0 if int(n) < 0 else int(n)
+        out = np.empty((n, self.pq.M), dtype=np.uint8)
+        self._bind_stream(False)
+        self._check(self._lib.fx_pq_get_codes(self._h, i0, n, ctypes.c_void_p(out.ctypes.data), _lib.MEM_HOST))
+        return out
+
+    @property
+    def codes(self) -> np.ndarray:
+        """faiss's ``index.codes``: every row's code, ``(ntotal, M)`` uint8."""
+        return self.get_codes()
+
+    def reset(self) -> None:
+        """Empties the index; the centroids stay, as in faiss."""
+        self._check(self._lib.fx_pq_reset(self._h))
+
+    def _counts(self):
+        a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.fx_pq_last_counts(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+    def last_fallbacks(self) -> int:
+        return self._counts()[0]
+
+    def last_exact_fallbacks(self) -> int:
+        return self._counts()[1]
+
+    def last_dropped_candidates(self) -> int:
+        return self._counts()[2]
+
+    def last_pq_plan(self) -> dict:
+        """The planner's outputs for the last search: ``path`` ("fused" /
+        "exact"), ``qtiles`` per pass, corpus ``splits`` per query tile,
+        ``xsplits`` of the exact scan, ``q_batch``, ``grid``."""
+        p, t_, s, x = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        qb, g = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.fx_pq_last_plan(self._h, ctypes.byref(p), ctypes.byref(t_), ctypes.byref(s),
+                                              ctypes.byref(x), ctypes.byref(qb), ctypes.byref(g)))
+        return {"path": "exact" if p.value else "fused", "qtiles": t_.value, "splits": s.value, "xsplits": x.value,
+                "q_batch": qb.value, "grid": g.value}
+
+    def profile(self, enable: bool = True) -> None:
+        """Record HIP events around the parts of every search pass."""
+        self._check(self._lib.fx_pq_profile(self._h, 1 if enable else 0))
+
+    def profile_read(self) -> dict:
+        """Milliseconds since the last read (waits for the stream): ``prep``,
+        ``scan``, ``refine`` (+ exact fallback), and the ``passes`` they cover."""
+        ms = [ctypes.c_double(0) for _ in range(3)]
+        n = ctypes.c_int64(0)
+        self._check(self._lib.fx_pq_profile_read(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(n)))
+        return {"prep": ms[0].value, "scan": ms[1].value, "refine": ms[2].value, "passes": n.value}
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                self._lib.fx_pq_free(h)
+            except Exception:  # noqa: BLE001 - interpreter shutdown
+                pass
+            self._h = None
+
+
+# ---------------------------------------------------------------------------
 # faiss.IndexIVFScalarQuantizer (include/fx_index.h "inverted file over 8-bit codes")
 # ---------------------------------------------------------------------------
 class IndexIVFScalarQuantizer(IndexIVFFlat):
@@ -1808,6 +2127,8 @@ def write_index(index, path: str) -> None:
         raise NotImplementedError("write_index of an IndexIVFFlat: write its quantizer and re-add the rows")
     if isinstance(index, IndexScalarQuantizer):
         raise NotImplementedError("write_index of an IndexScalarQuantizer: keep `trained` with numpy and re-add the rows")
+    if isinstance(index, IndexPQ):
+        raise NotImplementedError("write_index of an IndexPQ: keep `pq.centroids` with numpy and re-add the rows")
     index = _flat(index)
     check(index._lib.fx_index_write(index._h, str(path).encode()), index._lib)
 

@@ -35,6 +35,7 @@ class FAISSVectorStore:
     ivf = None  # the IndexIVFFlat / IndexIVFScalarQuantizer over the store's rows (build_ivf); dropped by every
                 # call that changes the rows
     sq = None   # the IndexScalarQuantizer over the store's rows (build_sq); dropped by the same calls
+    pq = None   # the IndexPQ over the store's rows (build_pq); dropped by the same calls
 
     def __new__(cls, *args, **kwargs):
         if cls._instance is None:
@@ -65,7 +66,7 @@ class FAISSVectorStore:
         """faiss_store.py:36-47.  The ids are recorded before the rows go in,
         and their count is not checked against the rows (as there)."""
         rows = self._as_rows(vectors)
-        self.ivf = self.sq = None
+        self.ivf = self.sq = self.pq = None
         self.doc_ids.extend(ids)
         self.index.add(rows)
         logger.info("add: %d ids -> ntotal %d", len(ids), self.index.ntotal)
@@ -126,7 +127,24 @@ class FAISSVectorStore:
             logger.error("build_sq failed: %s", e)
             raise
 
-    def search(self, query_vector, k: int = 5, allowed_ids=None, nprobe=None, sq: bool = False
+    def build_pq(self, M: int):
+        """An ``IndexPQ`` over the store's rows (extension): ``M`` bytes per
+        row, trained on and filled from the store's own index on the device.
+        Ids are row numbers, so ``doc_ids`` keeps mapping results.  Kept as
+        ``self.pq`` until a call changes the rows; ``search(..., pq=True)``
+        uses it.  Errors are logged and raised again, as in ``load_index``."""
+        try:
+            pq = _fx.IndexPQ(self.dimension, M, 8, _fx.METRIC_L2, device=self.device)
+            pq.train(self.index)
+            pq.add_from_index(self.index)
+            self.pq = pq
+            logger.info("build_pq: %d rows, %d bytes per row", self.index.ntotal, pq.code_size)
+            return pq
+        except Exception as e:
+            logger.error("build_pq failed: %s", e)
+            raise
+
+    def search(self, query_vector, k: int = 5, allowed_ids=None, nprobe=None, sq: bool = False, pq: bool = False
                ) -> Tuple[np.ndarray, List[int]]:
         """faiss_store.py:49-81: one query; index rows map to document ids,
         -1 and rows past the id list are dropped; on any error the result is
@@ -144,12 +162,20 @@ class FAISSVectorStore:
 
         ``sq=True`` (extension): search the ``IndexScalarQuantizer`` of
         ``build_sq`` -- the k nearest DECODED rows (no ``allowed_ids``, no
-        ``nprobe``, k <= ``FX_MAX_K``)."""
+        ``nprobe``, k <= ``FX_MAX_K``).
+
+        ``pq=True`` (extension): the same over the ``IndexPQ`` of ``build_pq``."""
         try:
             q = query_vector
             if isinstance(q, list):
                 q = np.array(q, dtype=np.float32)
-            if sq:
+            if pq:
+                if self.pq is None:
+                    raise RuntimeError("search(pq=True) needs build_pq first")
+                if allowed_ids is not None or nprobe is not None or sq:
+                    raise NotImplementedError("search(pq=True) takes no allowed_ids, no nprobe and no sq")
+                dist, rows = self.pq.search(q.reshape(1, -1), k)
+            elif sq:
                 if self.sq is None:
                     raise RuntimeError("search(sq=True) needs build_sq first")
                 if allowed_ids is not None or nprobe is not None:
@@ -214,7 +240,7 @@ class FAISSVectorStore:
             rows = [r for r in range(n_rows) if self.doc_ids[r] in gone]
             if not rows:
                 return 0
-            self.ivf = self.sq = None
+            self.ivf = self.sq = self.pq = None
             n = int(self.index.remove_ids(np.asarray(rows, dtype=np.int64)))
             dropped = set(rows)
             self.doc_ids = [doc for r, doc in enumerate(self.doc_ids) if r not in dropped]
@@ -256,7 +282,7 @@ class FAISSVectorStore:
         numbers; errors are logged and raised again."""
         path = filepath or self.index_path
         try:
-            self.ivf = self.sq = None
+            self.ivf = self.sq = self.pq = None
             self.index = _fx.read_index(path, dtype=self.dtype, device=self.device)
             if os.path.exists(path + ".mapping"):
                 with open(path + ".mapping", "rb") as f:
@@ -271,7 +297,7 @@ class FAISSVectorStore:
 
     def reset(self):
         """faiss_store.py:124-128: a fresh empty index, no ids."""
-        self.ivf = self.sq = None
+        self.ivf = self.sq = self.pq = None
         self.index = _fx.IndexFlatL2(self.dimension, dtype=self.dtype, device=self.device)
         self.doc_ids = []
         logger.info("reset")
