@@ -83,7 +83,7 @@ int fx_index_rows_of_ids(FxIndex* h, const int64_t* ids, int64_t n, int ids_mem,
     HIP_TRY(h->idm.ws.ensure(sort_bytes + 2 * nb));
     char* base = (char*)h->idm.ws.p;
     const void* dids = nullptr;
-    HIP_TRY(stage_in(h, h->idm.ws, ids, (size_t)n * 8, ids_mem, &dids, sort_bytes));
+    HIP_TRY(stage_in(h->stream(), h->idm.ws, ids, (size_t)n * 8, ids_mem, &dids, sort_bytes));
     int64_t* drows = rows_mem == FX_MEM_HOST ? (int64_t*)(base + sort_bytes + nb) : rows;
     HIP_TRY(launch_rows_of_labels(h->idm.labels, h->ntotal, (const int64_t*)dids, n, drows, base, sort_bytes, s));
     if (rows_mem == FX_MEM_HOST) HIP_TRY(hipMemcpyAsync(rows, drows, (size_t)n * 8, hipMemcpyDeviceToHost, s));

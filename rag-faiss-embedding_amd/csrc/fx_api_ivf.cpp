@@ -8,18 +8,188 @@
 // second copy of the payload while it runs (released again once the buffers
 // are swapped) and is O(ntotal) per add-then-search cycle; merging only the
 // appended tail is future work.
-#include "fx_host.h"
-#include "fx_plan.h"
+#include "fx_ivf_lists.h"
 
 using namespace fx;
 
+namespace fx {
+
+int ivf_quant_trained(const IvfLists& L, const char* who) {
+    if (L.quant->ntotal != L.nlist)
+        return set_err(FX_E_ARG, "%s: the index is not trained (the quantizer holds %lld of %lld centroids)", who,
+                       (long long)L.quant->ntotal, (long long)L.nlist);
+    return FX_OK;
+}
+
+int ivf_bad_error(const char* kind, int64_t bad, int64_t nlist) {
+    return set_err(FX_E_INTEGRITY, "%s: %lld rows were assigned outside [0, %lld) and belong to no list", kind,
+                   (long long)bad, (long long)nlist);
+}
+
+int ivf_read_bad(unsigned long long* bad, hipStream_t s, int64_t* out) {
+    unsigned long long h_bad = 0;
+    HIP_TRY(hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(bad, 0, 8, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = (int64_t)h_bad;
+    return FX_OK;
+}
+
+int ivf_add_mode(const IvfLists& L, int64_t ntotal, const int64_t* ids) {
+    if (ntotal > 0 && L.sequential && ids)
+        return set_err(FX_E_ARG, "add_with_ids not implemented for an index that holds rows without labels");
+    if (ntotal > 0 && !L.sequential && !ids)
+        return set_err(FX_E_ARG, "add does not make sense on an index with labels: use add_with_ids");
+    return FX_OK;
+}
+
+int ivf_regroup(const char* kind, IvfLists& L, const IvfRows& R, bool zero_incoming, unsigned long long* bad,
+                hipStream_t s) {
+    if (!L.dirty) return FX_OK;
+    L.h_off.assign((size_t)L.nlist + 1, 0);
+    if (R.n == 0) {
+        HIP_TRY(hipMemsetAsync(L.list_off, 0, (size_t)(L.nlist + 1) * 4, s));
+        L.max_list_rows = 0;
+        L.dirty = false;
+        return FX_OK;
+    }
+    // the second copy of the payload: released again when this call returns
+    DevBuf codes, norms, labels, row_list;
+    HIP_TRY(codes.ensure((size_t)R.cap_rows * R.row_bytes));
+    HIP_TRY(norms.ensure((size_t)R.cap_rows * 4));
+    HIP_TRY(labels.ensure(std::max<size_t>((size_t)R.cap_rows * 8, R.labels.bytes)));
+    HIP_TRY(row_list.ensure(std::max<size_t>((size_t)R.cap_rows * 4, R.row_list.bytes)));
+    if (zero_incoming) {
+        HIP_TRY(hipMemsetAsync(codes.p, 0, codes.bytes, s));
+        HIP_TRY(hipMemsetAsync(norms.p, 0, norms.bytes, s));
+    }
+    size_t ws = 0;
+    HIP_TRY(ivf_regroup_bytes(R.n, L.nlist, &ws));
+    HIP_TRY(L.rws.ensure(ws));
+    IvfRegroup r{};
+    r.n = R.n;
+    r.nlist = L.nlist;
+    r.row_bytes = R.row_bytes;
+    r.codes = (const char*)R.codes.p;
+    r.norms = (const float*)R.norms.p;
+    r.labels = (const int64_t*)R.labels.p;
+    r.row_list = (const int*)R.row_list.p;
+    r.dst_codes = (char*)codes.p;
+    r.dst_norms = (float*)norms.p;
+    r.dst_labels = (int64_t*)labels.p;
+    r.dst_row_list = (int*)row_list.p;
+    r.list_off = L.list_off;
+    r.max_rows = L.max_rows;
+    HIP_TRY(launch_ivf_regroup(r, L.rws.p, L.rws.bytes, s));
+    // the one synchronisation: the longest list (the planner's input), with the lists' offsets
+    int max_rows = 0;
+    HIP_TRY(hipMemcpyAsync(&max_rows, L.max_rows, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(L.h_off.data(), L.list_off, (size_t)(L.nlist + 1) * 4, hipMemcpyDeviceToHost, s));
+    int64_t nbad = 0;
+    if (const int rc = ivf_read_bad(bad, s, &nbad); rc != FX_OK) return rc;
+    // (the stream is idle: nothing reads the buffers that go out)
+    R.codes.swap(codes);
+    R.norms.swap(norms);
+    R.labels.swap(labels);
+    R.row_list.swap(row_list);
+    L.max_list_rows = max_rows;
+    L.dirty = false;
+    if (nbad > 0) return ivf_bad_error(kind, nbad, L.nlist);
+    return FX_OK;
+}
+
+int ivf_search_args(const char* kind, int64_t nq, int k, int nprobe, int q_dtype, int q_mem, int out_mem) {
+    if (nq < 0) return set_err(FX_E_ARG, "negative nq");
+    if (k < 1) return set_err(FX_E_ARG, "k must be positive (got %d)", k);
+    if (nprobe < 1) return set_err(FX_E_ARG, "nprobe must be positive (got %d)", nprobe);
+    if (!check_dtype(q_dtype)) return set_err(FX_E_ARG, "bad query dtype %d", q_dtype);
+    if (!valid_mem(q_mem) || !valid_mem(out_mem)) return set_err(FX_E_ARG, "bad q_mem / out_mem");
+    if (k > FX_MAX_K) return set_err(FX_E_UNSUPPORTED, "%s search: k = %d above FX_MAX_K = %d", kind, k, FX_MAX_K);
+    return FX_OK;
+}
+
+int ivf_probes(const char* kind, const IvfLists& L, int64_t nq, int nprobe, int* np) {
+    *np = (int)std::min<int64_t>(nprobe, L.nlist);
+    if (nq * *np >= (int64_t)INT32_MAX)
+        return set_err(FX_E_UNSUPPORTED, "%s search: nq * nprobe = %lld pairs (limit 2^31-1)", kind, (long long)(nq * *np));
+    if (*np > FX_MAX_K)
+        return set_err(FX_E_UNSUPPORTED, "%s search: nprobe = %d above %d (the coarse search's k)", kind, *np, FX_MAX_K);
+    return FX_OK;
+}
+
+hipError_t ivf_search_workspace(IvfLists& L, const IvfPlan& P, int64_t nq, int np, int k) {
+    L.last_plan[0] = P.path;
+    L.last_plan[1] = P.chunks;
+    L.last_plan[2] = P.slots;
+    L.last_qbatch = P.q_batch;
+    L.last_grid = P.grid;
+    const bool fused = P.path == IVF_PATH_FUSED;
+    const int64_t qb_max = std::min(P.q_batch, nq);
+    const size_t ncand = (size_t)qb_max * P.slots * (fused ? KP : k), nl = (size_t)(L.nlist + 1) * 4;
+    hipError_t e = L.coarse_d.ensure((size_t)qb_max * np * 4);
+    if (e == hipSuccess) e = L.coarse_i.ensure((size_t)qb_max * np * 8);
+    if (e == hipSuccess) e = L.flag.ensure((size_t)(qb_max + 1) * 4);
+    if (e == hipSuccess) e = L.cand_d.ensure(ncand * 4);
+    if (e == hipSuccess) e = L.cand_i.ensure(ncand * 4);
+    if (e != hipSuccess || !fused) return e;
+    e = L.pkeys.ensure((size_t)qb_max * np * 8);
+    if (e == hipSuccess) e = L.psorted.ensure((size_t)qb_max * np * 8);
+    if (e == hipSuccess) e = L.seg.ensure(nl);
+    if (e == hipSuccess) e = L.ngrp.ensure(nl);
+    if (e == hipSuccess) e = L.gbase.ensure(nl);
+    // hipCUB's temporaries for every pass size that occurs: full passes and a shorter last one
+    size_t tb = 0, tb_last = 0;
+    if (e == hipSuccess) e = ivf_pairs_temp_bytes(qb_max * np, L.nlist, &tb);
+    if (e == hipSuccess && nq % qb_max != 0) e = ivf_pairs_temp_bytes((nq % qb_max) * np, L.nlist, &tb_last);
+    if (e == hipSuccess) e = L.ptemp.ensure(std::max<size_t>(std::max(tb, tb_last), 16));
+    return e;
+}
+
+int ivf_coarse(IvfLists& L, hipStream_t s, int64_t qb, const void* q, int q_dtype, int np) {
+    BorrowQuant bq(L.quant, s);
+    HIP_TRY(bq.begin());
+    return do_search(L.quant, qb, q, q_dtype, FX_MEM_DEVICE, np, (float*)L.coarse_d.p, (int64_t*)L.coarse_i.p,
+                     FX_MEM_DEVICE);
+}
+
+hipError_t ivf_pairs(IvfLists& L, int* bad_cnt, int64_t qb, int np, hipStream_t s) {
+    IvfPairs pr{};
+    pr.coarse = (const int64_t*)L.coarse_i.p;
+    pr.npairs = qb * np;
+    pr.nlist = L.nlist;
+    pr.list_off = L.list_off;
+    pr.keys = (uint64_t*)L.pkeys.p;
+    pr.sorted = (uint64_t*)L.psorted.p;
+    pr.seg = (int*)L.seg.p;
+    pr.ngrp = (int*)L.ngrp.p;
+    pr.gbase = (int*)L.gbase.p;
+    pr.bad = bad_cnt;
+    return launch_ivf_pairs(pr, L.ptemp.p, L.ptemp.bytes, s);
+}
+
+int ivf_search_finish(const char* kind, SearchStats& st, const IvfLists& L, int device, hipStream_t s, int64_t nq, int k,
+                      float* D, const void* Dd, int64_t* I, const void* Id, int out_mem, int64_t ntotal) {
+    HIP_TRY(hipMemcpyAsync(st.pin_cnt, st.cnt, 12, hipMemcpyDeviceToHost, s));
+    st.counts_pending = true;
+    if (out_mem != FX_MEM_HOST) return FX_OK;
+    HIP_TRY(hipMemcpyAsync(D, Dd, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(I, Id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
+    if (const int rc = st.read_counts(device, s, L.quant); rc != FX_OK) return rc;
+    if (st.last_dropped == 0 && st.last_bad_probe == 0) return FX_OK;
+    return set_err(FX_E_INTEGRITY,
+                   "%s search: %lld candidate row ids outside [0, %lld) were dropped, %lld probed list numbers lay "
+                   "outside [0, %lld)",
+                   kind, (long long)st.last_dropped, (long long)ntotal, (long long)st.last_bad_probe, (long long)L.nlist);
+}
+
+}  // namespace fx
+
 namespace {
 
-int ivf_trained(const FxIvf* v, const char* who) {
-    if (v->quant->ntotal != v->nlist)
-        return set_err(FX_E_ARG, "%s: the index is not trained (the quantizer holds %lld of %lld centroids)", who,
-                       (long long)v->quant->ntotal, (long long)v->nlist);
-    return FX_OK;
+int regroup(FxIvf* v) {
+    FxIndex* p = v->pay;
+    const IvfRows rows{p->ntotal, p->cap_rows, p->row_bytes, p->codes, p->norms, p->idm.labels, v->row_list};
+    return ivf_regroup("ivf", *v, rows, false, v->bad, p->stream());
 }
 
 // buf holds at least `want` bytes, its first `keep` bytes carried over
@@ -33,102 +203,6 @@ hipError_t grow_keep(DevBuf& buf, size_t want, size_t keep, hipStream_t s) {
     if (e != hipSuccess) return e;
     buf.swap(nb);
     return hipSuccess;
-}
-
-int ivf_bad_error(int64_t bad, int64_t nlist) {
-    return set_err(FX_E_INTEGRITY, "ivf: %lld rows were assigned outside [0, %lld) and belong to no list", (long long)bad,
-                   (long long)nlist);
-}
-
-// the skipped-assignment count since the last read (the stream synchronised by the caller's copy), then 0 again
-int ivf_read_bad(FxIvf* v, int64_t* out) {
-    hipStream_t s = v->pay->stream();
-    unsigned long long bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, v->bad, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemsetAsync(v->bad, 0, 8, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *out = (int64_t)bad;
-    return FX_OK;
-}
-
-// the payload in list order (a no-op unless rows were added since)
-int ivf_regroup(FxIvf* v) {
-    if (!v->dirty) return FX_OK;
-    FxIndex* p = v->pay;
-    hipStream_t s = p->stream();
-    const int64_t n = p->ntotal;
-    v->h_off.assign((size_t)v->nlist + 1, 0);
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(v->list_off, 0, (size_t)(v->nlist + 1) * 4, s));
-        v->max_list_rows = 0;
-        v->dirty = false;
-        return FX_OK;
-    }
-    HIP_TRY(v->codes_alt.ensure((size_t)p->cap_rows * p->row_bytes));
-    HIP_TRY(v->norms_alt.ensure((size_t)p->cap_rows * 4));
-    HIP_TRY(v->labels_alt.ensure(std::max<size_t>((size_t)p->cap_rows * 8, p->idm.labels.bytes)));
-    HIP_TRY(v->row_list_alt.ensure(std::max<size_t>((size_t)p->cap_rows * 4, v->row_list.bytes)));
-    size_t ws = 0;
-    HIP_TRY(ivf_regroup_bytes(n, v->nlist, &ws));
-    HIP_TRY(v->rws.ensure(ws));
-    IvfRegroup r{};
-    r.n = n;
-    r.nlist = v->nlist;
-    r.row_bytes = p->row_bytes;
-    r.codes = p->codes;
-    r.norms = p->norms;
-    r.labels = p->idm.labels;
-    r.row_list = v->row_list;
-    r.dst_codes = v->codes_alt;
-    r.dst_norms = v->norms_alt;
-    r.dst_labels = v->labels_alt;
-    r.dst_row_list = v->row_list_alt;
-    r.list_off = v->list_off;
-    r.max_rows = v->max_rows;
-    HIP_TRY(launch_ivf_regroup(r, v->rws.p, v->rws.bytes, s));
-    // the one synchronisation: the longest list (the planner's input), with the lists' offsets
-    int max_rows = 0;
-    HIP_TRY(hipMemcpyAsync(&max_rows, v->max_rows, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(v->h_off.data(), v->list_off, (size_t)(v->nlist + 1) * 4, hipMemcpyDeviceToHost, s));
-    int64_t bad = 0;
-    if (const int rc = ivf_read_bad(v, &bad); rc != FX_OK) return rc;
-    // (the stream is idle: nothing reads the buffers that go out)
-    p->codes.swap(v->codes_alt);
-    p->norms.swap(v->norms_alt);
-    p->idm.labels.swap(v->labels_alt);
-    v->row_list.swap(v->row_list_alt);
-    // the second copy goes again: device memory is back at one payload
-    v->codes_alt.release();
-    v->norms_alt.release();
-    v->labels_alt.release();
-    v->row_list_alt.release();
-    v->max_list_rows = max_rows;
-    v->dirty = false;
-    if (bad > 0) return ivf_bad_error(bad, v->nlist);
-    return FX_OK;
-}
-
-int ivf_read_counts(FxIvf* v) {
-    if (v->counts_pending) {
-        DeviceGuard g(v->pay->device);
-        HIP_TRY(hipStreamSynchronize(v->pay->stream()));
-        v->last_dropped = v->pin_cnt[0];
-        v->last_fallbacks = v->pin_cnt[1];
-        v->last_bad_probe = v->pin_cnt[2];
-        v->counts_pending = false;
-        // the borrowed coarse search's own integrity count (of the last pass; its copies ran on this stream)
-        std::lock_guard<std::mutex> ql(v->quant->mu);
-        if (const int rc = read_counts(v->quant); rc != FX_OK) return rc;
-    }
-    return FX_OK;
-}
-
-int ivf_integrity(const FxIvf* v) {
-    return set_err(FX_E_INTEGRITY,
-                   "ivf search: %lld candidate row ids outside [0, %lld) were dropped, %lld probed list numbers lay "
-                   "outside [0, %lld)",
-                   (long long)v->last_dropped, (long long)v->pay->ntotal, (long long)v->last_bad_probe,
-                   (long long)v->nlist);
 }
 
 }  // namespace
@@ -151,6 +225,7 @@ int fx_ivf_create(FxIndex* quantizer, int d, int64_t nlist, int storage_dtype, i
     FxIvf* v = new FxIvf();
     v->quant = quantizer;
     v->pay = pay;
+    v->device = pay->device;
     v->nlist = nlist;
     v->h_off.assign((size_t)nlist + 1, 0);
     DeviceGuard g(pay->device);
@@ -159,14 +234,11 @@ int fx_ivf_create(FxIndex* quantizer, int d, int64_t nlist, int storage_dtype, i
     if (e == hipSuccess) e = v->max_rows.ensure(16);
     if (e == hipSuccess) e = v->bad.ensure(8);
     if (e == hipSuccess) e = hipMemset(v->bad, 0, 8);
-    if (e == hipSuccess) e = v->cnt.ensure(16);
-    if (e == hipSuccess) e = hipMemset(v->cnt, 0, 16);
-    if (e == hipSuccess) e = v->pin_cnt.ensure(16);
+    if (e == hipSuccess) e = v->init_counts();
     if (e != hipSuccess) {
         fx_ivf_free(v);
         return set_err(FX_E_HIP, "ivf init: %s", hipGetErrorString(e));
     }
-    v->pin_cnt[0] = v->pin_cnt[1] = v->pin_cnt[2] = 0;
     *out = v;
     return FX_OK;
 }
@@ -177,7 +249,7 @@ void fx_ivf_free(FxIvf* v) {
     {
         DeviceGuard g(pay->device);
         (void)hipStreamSynchronize(pay->stream());
-        for (hipEvent_t e : v->ev) (void)hipEventDestroy(e);
+        v->destroy_events();
         v->pay = nullptr;
         delete v;  // its buffers, with the device current
     }
@@ -186,20 +258,15 @@ void fx_ivf_free(FxIvf* v) {
 
 int fx_ivf_add(FxIvf* v, int64_t n, const void* x, int x_dtype, int x_mem, const int64_t* ids, int ids_mem) {
     // (the handle last: the other checks are then reachable without a device)
-    if (n < 0) return set_err(FX_E_ARG, "negative n");
-    if (!check_dtype(x_dtype)) return set_err(FX_E_ARG, "bad x dtype %d", x_dtype);
-    if (!valid_mem(x_mem)) return set_err(FX_E_ARG, "bad x_mem %d", x_mem);
+    if (const int rc = check_rows(n, x_dtype, x_mem); rc != FX_OK) return rc;
     if (ids && !valid_mem(ids_mem)) return set_err(FX_E_ARG, "bad ids_mem %d", ids_mem);
     if (!v) return set_err(FX_E_ARG, "null ivf index");
     if (n == 0) return FX_OK;
     if (!x) return set_err(FX_E_ARG, "null x");
     std::lock_guard<std::mutex> lk(v->mu);
-    if (const int rc = ivf_trained(v, "ivf add"); rc != FX_OK) return rc;
+    if (const int rc = ivf_quant_trained(*v, "ivf add"); rc != FX_OK) return rc;
     FxIndex* p = v->pay;
-    if (p->ntotal > 0 && v->sequential && ids)
-        return set_err(FX_E_ARG, "add_with_ids not implemented for an index that holds rows without labels");
-    if (p->ntotal > 0 && !v->sequential && !ids)
-        return set_err(FX_E_ARG, "add does not make sense on an index with labels: use add_with_ids");
+    if (const int rc = ivf_add_mode(*v, p->ntotal, ids); rc != FX_OK) return rc;
     if (p->ntotal + n + TILE_R >= (int64_t)INT32_MAX)
         return set_err(FX_E_UNSUPPORTED, "ivf: more than 2^31-1 rows");
     DeviceGuard g(p->device);
@@ -242,85 +309,50 @@ int fx_ivf_add(FxIvf* v, int64_t n, const void* x, int x_dtype, int x_mem, const
     v->dirty = true;
     if (x_mem == FX_MEM_HOST) {  // a host call waits for its work: its skipped rows are known now
         int64_t bad = 0;
-        if (const int rc = ivf_read_bad(v, &bad); rc != FX_OK) return rc;
-        if (bad > 0) return ivf_bad_error(bad, v->nlist);
+        if (const int rc = ivf_read_bad(v->bad, s, &bad); rc != FX_OK) return rc;
+        if (bad > 0) return ivf_bad_error("ivf", bad, v->nlist);
     }
     return FX_OK;
 }
 
 int fx_ivf_search(FxIvf* v, int64_t nq, const void* q, int q_dtype, int q_mem, int k, int nprobe, float* D, int64_t* I,
                   int out_mem) {
-    if (nq < 0) return set_err(FX_E_ARG, "negative nq");
-    if (k < 1) return set_err(FX_E_ARG, "k must be positive (got %d)", k);
-    if (nprobe < 1) return set_err(FX_E_ARG, "nprobe must be positive (got %d)", nprobe);
-    if (!check_dtype(q_dtype)) return set_err(FX_E_ARG, "bad query dtype %d", q_dtype);
-    if (!valid_mem(q_mem) || !valid_mem(out_mem)) return set_err(FX_E_ARG, "bad q_mem / out_mem");
-    if (k > FX_MAX_K) return set_err(FX_E_UNSUPPORTED, "ivf search: k = %d above FX_MAX_K = %d", k, FX_MAX_K);
+    if (const int rc = ivf_search_args("ivf", nq, k, nprobe, q_dtype, q_mem, out_mem); rc != FX_OK) return rc;
     if (!v) return set_err(FX_E_ARG, "null ivf index");
     std::lock_guard<std::mutex> lk(v->mu);
-    if (const int rc = ivf_trained(v, "ivf search"); rc != FX_OK) return rc;
+    if (const int rc = ivf_quant_trained(*v, "ivf search"); rc != FX_OK) return rc;
     if (nq == 0) return FX_OK;
     if (!q || !D || !I) return set_err(FX_E_ARG, "null buffer");
-    const int np = (int)std::min<int64_t>(nprobe, v->nlist);
-    if (nq * np >= (int64_t)INT32_MAX)
-        return set_err(FX_E_UNSUPPORTED, "ivf search: nq * nprobe = %lld pairs (limit 2^31-1)", (long long)(nq * np));
-    if (np > FX_MAX_K)
-        return set_err(FX_E_UNSUPPORTED, "ivf search: nprobe = %d above %d (the coarse search's k)", np, FX_MAX_K);
+    int np = 0;
+    if (const int rc = ivf_probes("ivf", *v, nq, nprobe, &np); rc != FX_OK) return rc;
     FxIndex* p = v->pay;
     DeviceGuard g(p->device);
     if (!g.ok) return set_err(FX_E_HIP, "hipSetDevice(%d) failed", p->device);
-    if (const int rc = ivf_regroup(v); rc != FX_OK) return rc;
+    if (const int rc = regroup(v); rc != FX_OK) return rc;
     // (an earlier device search's counts, if nobody asked for them, give way to this search's)
-    v->counts_pending = false;
-    v->last_fallbacks = v->last_dropped = v->last_bad_probe = 0;
+    v->clear_counts();
     if (p->ntotal == 0) return fill_missing(p, nq, k, D, I, out_mem);
 
     hipStream_t s = p->stream();
     const IvfPlan P = plan_ivf(nq, np, v->nlist, v->max_list_rows, p->ntotal, k, p->row_bytes);
-    v->last_plan[0] = P.path;
-    v->last_plan[1] = P.chunks;
-    v->last_plan[2] = P.slots;
-    v->last_qbatch = P.q_batch;
-    v->last_grid = P.grid;
     const int qes = dtype_size(q_dtype);
     const void* qdev = nullptr;
-    HIP_TRY(stage_in(p, v->qin, q, (size_t)nq * p->d * qes, q_mem, &qdev));
-    const bool host_out = out_mem == FX_MEM_HOST;
-    float* Dd = D;
-    int64_t* Id = I;
-    if (host_out) {
-        HIP_TRY(v->outD.ensure((size_t)nq * k * 4));
-        HIP_TRY(v->outI.ensure((size_t)nq * k * 8));
-        Dd = (float*)v->outD.p;
-        Id = (int64_t*)v->outI.p;
-    }
+    HIP_TRY(stage_in(s, v->qin, q, (size_t)nq * p->d * qes, q_mem, &qdev));
+    void *Dd = D, *Id = I;
+    HIP_TRY(out_buf(v->outD, D, (size_t)nq * k * 4, out_mem, &Dd));
+    HIP_TRY(out_buf(v->outI, I, (size_t)nq * k * 8, out_mem, &Id));
     HIP_TRY(hipMemsetAsync(v->cnt, 0, 16, s));
     const int C = P.chunks, slots = P.slots;
     const bool fused = P.path == IVF_PATH_FUSED;
     const int64_t qb_max = std::min(P.q_batch, nq);
     const int64_t nq_pad_max = round_up(qb_max, QPAD);
-    HIP_TRY(v->coarse_d.ensure((size_t)qb_max * np * 4));
-    HIP_TRY(v->coarse_i.ensure((size_t)qb_max * np * 8));
-    HIP_TRY(v->flag.ensure((size_t)(qb_max + 1) * 4));
+    HIP_TRY(ivf_search_workspace(*v, P, nq, np, k));
     HIP_TRY(v->qb.f32.ensure((size_t)nq_pad_max * p->kdim * 4));
-    const size_t ncand = (size_t)qb_max * slots * (fused ? KP : k);
-    HIP_TRY(v->cand_d.ensure(ncand * 4));
-    HIP_TRY(v->cand_i.ensure(ncand * 4));
     if (fused) {
         HIP_TRY(v->qb.op.ensure((size_t)nq_pad_max * p->row_bytes));
         HIP_TRY(v->qb.eps.ensure((size_t)qb_max * 4));
         HIP_TRY(v->qb.rho.ensure((size_t)qb_max * 4));
         HIP_TRY(v->qb.shift.ensure((size_t)qb_max * 8));
-        HIP_TRY(v->pkeys.ensure((size_t)qb_max * np * 8));
-        HIP_TRY(v->psorted.ensure((size_t)qb_max * np * 8));
-        HIP_TRY(v->seg.ensure((size_t)(v->nlist + 1) * 4));
-        HIP_TRY(v->ngrp.ensure((size_t)(v->nlist + 1) * 4));
-        HIP_TRY(v->gbase.ensure((size_t)(v->nlist + 1) * 4));
-        // hipCUB's temporaries for every pass size that occurs: full passes and a shorter last one
-        size_t tb = 0, tb_last = 0;
-        HIP_TRY(ivf_pairs_temp_bytes(qb_max * np, v->nlist, &tb));
-        if (nq % qb_max != 0) HIP_TRY(ivf_pairs_temp_bytes((nq % qb_max) * np, v->nlist, &tb_last));
-        HIP_TRY(v->ptemp.ensure(std::max<size_t>(std::max(tb, tb_last), 16)));
     }
     int* n_flag = (int*)v->flag.p;
 
@@ -328,20 +360,10 @@ int fx_ivf_search(FxIvf* v, int64_t nq, const void* q, int q_dtype, int q_mem, i
         const int64_t qb = std::min(qb_max, nq - q0);
         const void* qp = (const char*)qdev + (size_t)q0 * p->d * qes;
         hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        if (v->profile) {
-            for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-            v->ev.insert(v->ev.end(), ev, ev + 5);
-            HIP_TRY(hipEventRecord(ev[0], s));
-        }
+        HIP_TRY(v->begin_pass(ev, 5, s));
         // 1. coarse: the quantizer's exact top-np search names the probed lists
-        {
-            BorrowQuant bq(v->quant, s);
-            HIP_TRY(bq.begin());
-            const int rc = do_search(v->quant, qb, qp, q_dtype, FX_MEM_DEVICE, np, (float*)v->coarse_d.p,
-                                     (int64_t*)v->coarse_i.p, FX_MEM_DEVICE);
-            if (rc != FX_OK) return rc;
-        }
-        if (v->profile) HIP_TRY(hipEventRecord(ev[1], s));
+        if (const int rc = ivf_coarse(*v, s, qb, qp, q_dtype, np); rc != FX_OK) return rc;
+        HIP_TRY(v->mark(ev[1], s));
         IvfExact ex{};
         ex.codes = p->codes;
         ex.row_bytes = p->row_bytes;
@@ -357,34 +379,21 @@ int fx_ivf_search(FxIvf* v, int64_t nq, const void* q, int q_dtype, int q_mem, i
         ex.cd = (float*)v->cand_d.p;
         ex.ci = (int*)v->cand_i.p;
         ex.labels = p->idm.labels;
-        ex.D = Dd + q0 * k;
-        ex.I = Id + q0 * k;
+        ex.D = (float*)Dd + q0 * k;
+        ex.I = (int64_t*)Id + q0 * k;
         if (!fused) {
             // the exact path for the whole pass: every query "flagged"
             HIP_TRY(launch_f32_queries(qp, q_dtype, qb, p->d, p->kdim, (float*)v->qb.f32.p, s));
             HIP_TRY(launch_ivf_count_bad(ex.coarse, qb * np, v->nlist, v->cnt + 2, s));
             HIP_TRY(launch_ivf_flag_all(n_flag, qb, s));
-            if (v->profile) HIP_TRY(hipEventRecord(ev[2], s));
+            HIP_TRY(v->mark(ev[2], s));
             HIP_TRY(launch_ivf_exact(p->dtype, p->metric, ex, s));
-            if (v->profile) {  // (the exact scan is this path's "list scan"; it has no refine)
-                HIP_TRY(hipEventRecord(ev[3], s));
-                HIP_TRY(hipEventRecord(ev[4], s));
-            }
+            HIP_TRY(v->mark(ev[3], s));  // (the exact scan is this path's "list scan"; it has no refine)
+            HIP_TRY(v->mark(ev[4], s));
             continue;
         }
         // 2. the pass's (query, list) pairs grouped by list
-        IvfPairs pr{};
-        pr.coarse = ex.coarse;
-        pr.npairs = qb * np;
-        pr.nlist = v->nlist;
-        pr.list_off = v->list_off;
-        pr.keys = (uint64_t*)v->pkeys.p;
-        pr.sorted = (uint64_t*)v->psorted.p;
-        pr.seg = (int*)v->seg.p;
-        pr.ngrp = (int*)v->ngrp.p;
-        pr.gbase = (int*)v->gbase.p;
-        pr.bad = v->cnt + 2;
-        HIP_TRY(launch_ivf_pairs(pr, v->ptemp.p, v->ptemp.bytes, s));
+        HIP_TRY(ivf_pairs(*v, v->cnt + 2, qb, np, s));
         // query operands over the stored rows with plain norms (no image), as range_search prepares them
         const int64_t nq_pad = round_up(qb, QPAD);
         PrepParams pp{};
@@ -402,15 +411,15 @@ int fx_ivf_search(FxIvf* v, int64_t nq, const void* q, int q_dtype, int q_mem, i
         sc.qop = (const char*)v->qb.op.p;
         sc.np = np;
         sc.C = C;
-        sc.sorted = pr.sorted;
-        sc.seg = pr.seg;
-        sc.gbase = pr.gbase;
+        sc.sorted = (uint64_t*)v->psorted.p;
+        sc.seg = (int*)v->seg.p;
+        sc.gbase = (int*)v->gbase.p;
         sc.cand_d = (float*)v->cand_d.p;
         sc.cand_i = (int*)v->cand_i.p;
         sc.grid = (qb * np / TILE_Q + std::min<int64_t>(v->nlist, qb * np)) * C;
-        if (v->profile) HIP_TRY(hipEventRecord(ev[2], s));
+        HIP_TRY(v->mark(ev[2], s));
         HIP_TRY(launch_ivf_scan(p->dtype, p->metric, sc, s));
-        if (v->profile) HIP_TRY(hipEventRecord(ev[3], s));
+        HIP_TRY(v->mark(ev[3], s));
 #ifdef FX_DIAG
         // FX_IVF_CAND (read when the index was created): the pass's scan lists, probed lists and list
         // offsets appended to the file, before the refine reads the lists and the exact scan writes over them:
@@ -456,15 +465,9 @@ int fx_ivf_search(FxIvf* v, int64_t nq, const void* q, int q_dtype, int q_mem, i
         // 5. the flagged queries' exact lists (device-gated; the candidate buffers are free again)
         HIP_TRY(launch_ivf_exact(p->dtype, p->metric, ex, s));
         HIP_TRY(launch_ivf_accum(v->cnt + 1, n_flag, s));
-        if (v->profile) HIP_TRY(hipEventRecord(ev[4], s));
+        HIP_TRY(v->mark(ev[4], s));
     }
-    HIP_TRY(hipMemcpyAsync(v->pin_cnt, v->cnt, 12, hipMemcpyDeviceToHost, s));
-    v->counts_pending = true;
-    if (!host_out) return FX_OK;
-    HIP_TRY(hipMemcpyAsync(D, Dd, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(I, Id, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
-    if (const int rc = ivf_read_counts(v); rc != FX_OK) return rc;
-    return v->last_dropped > 0 || v->last_bad_probe > 0 ? ivf_integrity(v) : FX_OK;
+    return ivf_search_finish("ivf", *v, *v, p->device, s, nq, k, D, Dd, I, Id, out_mem, p->ntotal);
 }
 
 int fx_ivf_reset(FxIvf* v) {
@@ -487,30 +490,11 @@ int fx_ivf_ntotal(const FxIvf* v, int64_t* out) {
     return FX_OK;
 }
 
-int fx_ivf_list_sizes(FxIvf* v, int64_t* out) {
-    if (!v || !out) return set_err(FX_E_ARG, "null argument");
-    std::lock_guard<std::mutex> lk(v->mu);
-    DeviceGuard g(v->pay->device);
-    if (const int rc = ivf_regroup(v); rc != FX_OK) return rc;
-    for (int64_t l = 0; l < v->nlist; ++l) out[l] = (int64_t)v->h_off[l + 1] - v->h_off[l];
-    return FX_OK;
-}
+int fx_ivf_list_sizes(FxIvf* v, int64_t* out) { return ivf_list_sizes(v, regroup, out); }
 
 int fx_ivf_list_ids(FxIvf* v, int64_t list, int64_t* out, int64_t cap, int64_t* n) {
-    if (!v || !n) return set_err(FX_E_ARG, "null argument");
-    std::lock_guard<std::mutex> lk(v->mu);
-    if (list < 0 || list >= v->nlist)
-        return set_err(FX_E_ARG, "ivf list_ids: list %lld outside [0, %lld)", (long long)list, (long long)v->nlist);
-    DeviceGuard g(v->pay->device);
-    if (const int rc = ivf_regroup(v); rc != FX_OK) return rc;
-    const int64_t r0 = v->h_off[list], cnt = (int64_t)v->h_off[list + 1] - r0;
-    *n = cnt;
-    if (cnt == 0 || cap <= 0) return FX_OK;
-    if (!out) return set_err(FX_E_ARG, "null buffer");
-    hipStream_t s = v->pay->stream();
-    HIP_TRY(hipMemcpyAsync(out, v->pay->idm.labels + r0, (size_t)std::min(cnt, cap) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return FX_OK;
+    if (!v) return set_err(FX_E_ARG, "null argument");
+    return ivf_list_ids(v, "ivf", regroup, v->pay->idm.labels, list, out, cap, n);
 }
 
 int fx_ivf_set_stream(FxIvf* v, void* stream) {
@@ -520,55 +504,19 @@ int fx_ivf_set_stream(FxIvf* v, void* stream) {
 }
 
 int fx_ivf_last_counts(FxIvf* v, int64_t* fallbacks, int64_t* exact_fallbacks, int64_t* dropped) {
-    if (!v || !fallbacks || !exact_fallbacks || !dropped) return set_err(FX_E_ARG, "null argument");
-    std::lock_guard<std::mutex> lk(v->mu);
-    if (const int rc = ivf_read_counts(v); rc != FX_OK) return rc;
-    // (a flagged query goes straight to the exact list scan: both counts are the same)
-    *fallbacks = v->last_fallbacks;
-    *exact_fallbacks = v->last_fallbacks;
-    *dropped = v->last_dropped + v->last_bad_probe;
-    return FX_OK;
+    return handle_last_counts(v, v ? v->quant : nullptr, fallbacks, exact_fallbacks, dropped);
 }
 
-int fx_ivf_profile(FxIvf* v, int enable) {
-    if (!v) return set_err(FX_E_ARG, "null ivf index");
-    std::lock_guard<std::mutex> lk(v->mu);
-    v->profile = enable != 0;
-    return FX_OK;
-}
+int fx_ivf_profile(FxIvf* v, int enable) { return handle_profile(v, "ivf", enable); }
 
 int fx_ivf_profile_read(FxIvf* v, double* coarse_ms, double* pairs_ms, double* scan_ms, double* refine_ms,
                         int64_t* passes) {
-    if (!v || !coarse_ms || !pairs_ms || !scan_ms || !refine_ms || !passes) return set_err(FX_E_ARG, "null argument");
-    std::lock_guard<std::mutex> lk(v->mu);
-    DeviceGuard g(v->pay->device);
-    HIP_TRY(hipStreamSynchronize(v->pay->stream()));
-    double ms[4] = {0, 0, 0, 0};
-    float t = 0;
-    for (size_t i = 0; i + 4 < v->ev.size(); i += 5)
-        for (int part = 0; part < 4; ++part) {
-            HIP_TRY(hipEventElapsedTime(&t, v->ev[i + part], v->ev[i + part + 1]));
-            ms[part] += t;
-        }
-    *passes = (int64_t)(v->ev.size() / 5);
-    for (hipEvent_t e : v->ev) (void)hipEventDestroy(e);
-    v->ev.clear();
-    *coarse_ms = ms[0];
-    *pairs_ms = ms[1];
-    *scan_ms = ms[2];
-    *refine_ms = ms[3];
-    return FX_OK;
+    double* const ms[] = {coarse_ms, pairs_ms, scan_ms, refine_ms};
+    return handle_profile_read(v, ms, passes);
 }
 
 int fx_ivf_last_plan(FxIvf* v, int* path, int* chunks, int* slots, int64_t* q_batch, int64_t* grid) {
-    if (!v || !path || !chunks || !slots || !q_batch || !grid) return set_err(FX_E_ARG, "null argument");
-    std::lock_guard<std::mutex> lk(v->mu);
-    *path = v->last_plan[0];
-    *chunks = v->last_plan[1];
-    *slots = v->last_plan[2];
-    *q_batch = v->last_qbatch;
-    *grid = v->last_grid;
-    return FX_OK;
+    return ivf_last_plan(v, path, chunks, slots, q_batch, grid);
 }
 
 }  // extern "C"

@@ -62,7 +62,7 @@ int fx_index_range_search(FxIndex* h, int64_t nq, const void* q, int q_dtype, in
     const size_t qb = (size_t)nq * h->d * dtype_size(q_dtype);
     if (q_mem == FX_MEM_HOST) RG_ALLOC(h->rg.qin, qb);
     const void* qdev = nullptr;
-    HIP_TRY(stage_in(h, h->rg.qin, q, qb, q_mem, &qdev));
+    HIP_TRY(stage_in(h->stream(), h->rg.qin, q, qb, q_mem, &qdev));
     const int64_t nq_pad = round_up(nq, QPAD);
     RG_ALLOC(h->rg.f32, (size_t)nq_pad * h->kdim * 4);
     RG_ALLOC(h->rg.op, (size_t)nq_pad * h->row_bytes);

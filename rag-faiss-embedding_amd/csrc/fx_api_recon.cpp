@@ -83,7 +83,7 @@ int fx_index_reconstruct_batch(FxIndex* h, int64_t n, const int64_t* keys, int k
     if (!g.ok) return set_err(FX_E_HIP, "hipSetDevice(%d) failed", h->device);
     hipStream_t s = h->stream();
     const void* staged = nullptr;
-    HIP_TRY(stage_in(h, h->rc.in, keys, (size_t)n * 8, keys_mem, &staged));
+    HIP_TRY(stage_in(h->stream(), h->rc.in, keys, (size_t)n * 8, keys_mem, &staged));
     const int64_t* dkeys = (const int64_t*)staged;
     int64_t id_offset = h->id_offset;
     if (h->has_ids) {  // labels -> rows (an unknown label: -1 -> a NaN row)
@@ -197,8 +197,8 @@ int fx_index_compute_distance_subset(FxIndex* h, int64_t nq, const void* q, int 
     const bool stage_q = q_mem == FX_MEM_HOST, stage_k = keys_mem == FX_MEM_HOST;
     if (stage_q || stage_k) HIP_TRY(h->rc.in.ensure(koff + (size_t)n * 8));
     const void *qdev = nullptr, *staged = nullptr;
-    HIP_TRY(stage_in(h, h->rc.in, q, qbytes, q_mem, &qdev));
-    HIP_TRY(stage_in(h, h->rc.in, keys, (size_t)n * 8, keys_mem, &staged, koff));
+    HIP_TRY(stage_in(h->stream(), h->rc.in, q, qbytes, q_mem, &qdev));
+    HIP_TRY(stage_in(h->stream(), h->rc.in, keys, (size_t)n * 8, keys_mem, &staged, koff));
     const int64_t* dkeys = (const int64_t*)staged;
     // the queries once as padded fp32 [nq][kdim], in a buffer of this call's own (not a search's)
     HIP_TRY(h->rc.qf32.ensure((size_t)nq * h->kdim * 4));

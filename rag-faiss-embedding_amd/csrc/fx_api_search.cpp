@@ -551,7 +551,7 @@ int fx::do_search_hugek(FxIndex* h, int64_t nq, const void* q, int q_dtype, int 
                         int out_mem, bool row_ids) {
     hipStream_t s = h->stream();
     const void* qdev = nullptr;
-    HIP_TRY(stage_in(h, h->qin, q, (size_t)nq * h->d * dtype_size(q_dtype), q_mem, &qdev));
+    HIP_TRY(stage_in(h->stream(), h->qin, q, (size_t)nq * h->d * dtype_size(q_dtype), q_mem, &qdev));
     float* Dd = D;
     int64_t* Id = I;
     if (out_mem == FX_MEM_HOST) {

@@ -88,7 +88,7 @@ int fx_selector_create(FxIndex* h, int kind, const void* data, int64_t n, int da
             if (e == hipSuccess && sort_bytes + (stage ? bytes : 0) > 0)
                 e = h->idm.ws.ensure(sort_bytes + (stage ? bytes : 0));
             const void* dev = data;
-            if (e == hipSuccess && stage) e = stage_in(h, h->idm.ws, data, bytes, data_mem, &dev, sort_bytes);
+            if (e == hipSuccess && stage) e = stage_in(h->stream(), h->idm.ws, data, bytes, data_mem, &dev, sort_bytes);
             if (e == hipSuccess)
                 e = kind == FX_SEL_IDS
                         ? launch_sel_ids_lbl(labels, (const int64_t*)dev, n, nt, invert != 0, sel->mask, h->idm.ws.p,
@@ -104,7 +104,7 @@ int fx_selector_create(FxIndex* h, int kind, const void* data, int64_t n, int da
     } else if (e == hipSuccess) {
         const size_t bytes = (size_t)n * (kind == FX_SEL_IDS ? 8 : 1);
         const void* dev = data;
-        if (n > 0) e = stage_in(h, staged, data, bytes, data_mem, &dev);
+        if (n > 0) e = stage_in(h->stream(), staged, data, bytes, data_mem, &dev);
         if (e == hipSuccess)
             e = kind == FX_SEL_IDS ? launch_sel_ids((const int64_t*)dev, n, off, nt, invert != 0, sel->mask, s)
                                    : launch_sel_bitmap((const uint8_t*)dev, n, off, nt, invert != 0, sel->mask, s);

@@ -2,7 +2,8 @@
 // fx_api_*.cpp, fx_plan.cpp; never a .hip file): error reporting, the owning
 // buffers, the index's options and state, and the few helpers that cross files.
 // Each feature's state is a member struct of FxIndex, declared here beside the
-// prototypes of the file that owns it.
+// prototypes of the file that owns it; the other index handles are built from
+// the shared parts of fx_api_handle.cpp (Handle, SearchStats, CodeRows).
 #pragma once
 #include "../../include/fx_index.h"
 
@@ -367,9 +368,9 @@ int check_add_args(const FxIndex* h, int64_t n, const void* x, int x_dtype);
 // (which keeps them out of the scan's candidate lists)
 hipError_t blank_rows(FxIndex* h, int64_t r0, int64_t r1, hipStream_t s);
 // Input of a call -> where the kernels read it: device memory is used where it
-// lies (*dev = src); host memory is copied, on the index's stream, into `buf`
-// (grown to offset + bytes) at `offset`.
-hipError_t stage_in(FxIndex* h, DevBuf& buf, const void* src, size_t bytes, int mem, const void** dev,
+// lies (*dev = src); host memory is copied, on stream s, into `buf` (grown to
+// offset + bytes) at `offset`.
+hipError_t stage_in(hipStream_t s, DevBuf& buf, const void* src, size_t bytes, int mem, const void** dev,
                     size_t offset = 0);
 
 // ---- fx_api_search.cpp ---------------------------------------------------------
@@ -543,43 +544,6 @@ struct FxIndex {
     fx::IndexShape shape() const { return {ntotal, row_bytes, dtype, metric, img_kind}; }
 };
 
-// ---- fx_api_ivf.cpp ------------------------------------------------------------
-
-// An inverted-file index (include/fx_index.h, fx_ivf.hip).  `quant` is the
-// caller's coarse quantizer (borrowed); `pay` the payload it owns: a labelled
-// flat index whose rows are in list order once `dirty` is false.  row_list[r] is
-// the list of payload row r (nlist: an assignment outside the lists).
-struct FxIvf {
-    FxIndex* quant = nullptr;
-    FxIndex* pay = nullptr;
-    int64_t nlist = 0;
-    bool dirty = false;         // rows were appended since the last regroup
-    bool sequential = false;    // ids are ntotal .. (fx_ivf_add without ids); decided by the first add
-    int64_t max_list_rows = 0;  // of the last regroup
-    std::vector<int> h_off;     // list_off on the host, read back with it ([nlist + 1])
-    fx::DevArr<int> row_list, row_list_alt, list_off, max_rows;
-    fx::DevArr<char> codes_alt;
-    fx::DevArr<float> norms_alt;
-    fx::DevArr<int64_t> labels_alt;
-    fx::DevBuf rws;             // the regroup's sort workspace
-    fx::DevBuf assign, ids;     // a chunk's k = 1 search results; sequential ids of an add
-    fx::DevArr<unsigned long long> bad;  // assignments outside [0, nlist) since the last read
-    // search workspace
-    fx::QueryBufs qb;
-    fx::DevBuf qin, coarse_d, coarse_i, pkeys, psorted, seg, ngrp, gbase, ptemp, cand_d, cand_i, flag, outD, outI;
-    fx::DevArr<int> cnt;        // [0] dropped candidate ids, [1] queries flagged, [2] coarse entries outside the lists
-    fx::PinArr<int> pin_cnt;
-    bool counts_pending = false;
-    int64_t last_fallbacks = 0, last_dropped = 0, last_bad_probe = 0;
-    int last_plan[3] = {0, 0, 0};  // path, chunks, slots
-    int64_t last_qbatch = 0, last_grid = 0;
-    // profiling (fx_ivf_profile): 5 events per pass -- start, after the coarse search, after pairs + query
-    // preparation, after the list scan, after refine + exact fallback
-    bool profile = false;
-    std::vector<hipEvent_t> ev;
-    std::mutex mu;
-};
-
 // The quantizer's searches run on the borrowing index's stream for the duration
 // of a call (the quantizer locked): both directions ordered on the device, as
 // fx_index_set_stream orders a switch.
@@ -606,111 +570,223 @@ struct BorrowQuant {
     }
 };
 
-// ---- fx_api_sq.cpp -------------------------------------------------------------
+// ---- fx_api_handle.cpp: what the indexes beside the flat one share -------------
+//
+// FxSq, FxPq and FxIvfSq are a Handle (stream, options, lock, counts, profile)
+// over CodeRows (their payload); FxSq and FxPq share FlatCodes and its search
+// driver (fx_flat_codes.h); FxIvf and FxIvfSq share IvfLists (fx_ivf_lists.h).
 
-// A scalar-quantizer index (include/fx_index.h, fx_sq.hip): 8-bit signed codes
-// [cap_rows][row_bytes] with a whole tile past the last row, the rows' constants
-// n_c, the trained tables [vmin | vdiff] and the index-wide bound words.
-struct FxSq {
-    int d = 0, qtype = 0, metric = fx::L2, device = 0, row_bytes = 0;
-    int64_t ntotal = 0, cap_rows = 0;
-    bool trained = false;
-    bool train_open = false;  // fx_sq_train calls with more != 0 have accumulated min / max
-    fx::DevArr<char> codes;
-    fx::DevArr<float> nc, tables;
-    fx::DevArr<unsigned> words, mm;
-    fx::DevArr<unsigned long long> bad;
-    hipStream_t own_stream = nullptr, user_stream = nullptr;
-    hipEvent_t switch_ev = nullptr;
-    fx::Options opt;  // (force_fallback of the diagnostic build, read from the environment at creation)
-    // workspace of add / search / the codec
-    fx::DevBuf in, qf32, planes, sigma, eps, rho, shift, cand_d, cand_i, flag, outD, outI, io;
-    fx::DevArr<int> cnt;  // [0] dropped candidate ids, [1] queries flagged, [2] scratch (the exact path's)
-    fx::PinArr<int> pin_cnt;
+namespace fx {
+
+// D / I of a search over an empty index, written through host vectors (FxIndex
+// fills with memsets: fx_api_search.cpp)
+int fill_missing(hipStream_t s, int metric, int64_t nq, int k, float* D, int64_t* I, int out_mem);
+// where a call's result is computed: the caller's device memory, or `io` for a host caller ...
+hipError_t out_buf(DevBuf& io, void* out, size_t bytes, int out_mem, void** od);
+// ... and its way back: copied out and waited for (wait: a host input the call staged must be waited for too)
+int finish_out(hipStream_t s, void* out, const void* od, size_t bytes, int out_mem, bool wait = false);
+// "<kind> <call>: the index is not trained"
+int need_trained(bool trained, const char* kind, const char* call);
+// the checks of a call that takes rows x [n][d] (the handle's own check comes after them)
+int check_rows(int64_t n, int x_dtype, int x_mem);
+// a trained table [vmin | vdiff] as the scalar quantizers accept it
+int sq_check_tables(const char* kind, int d, const float* trained);
+
+// Rows x [n][d] through the bounded staging buffer `in` (<= 256 MiB a chunk, or
+// `chunk` rows): body(xd, r0, nr) per chunk, and one synchronisation per chunk
+// when x is host memory (the staging buffer is reused).
+template <class Body>
+int staged_rows(hipStream_t s, DevBuf& in, int64_t n, const void* x, size_t row_bytes, int x_mem, int64_t chunk,
+                Body body) {
+    if (chunk <= 0)
+        chunk = x_mem == FX_MEM_DEVICE ? std::max<int64_t>(n, 1) : std::max<int64_t>(1, (256ll << 20) / (int64_t)row_bytes);
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int64_t nr = std::min(chunk, n - r0);
+        const void* xd = nullptr;
+        HIP_TRY(stage_in(s, in, (const char*)x + (size_t)r0 * row_bytes, (size_t)nr * row_bytes, x_mem, &xd));
+        if (const int rc = body(xd, r0, nr); rc != FX_OK) return rc;
+        if (x_mem == FX_MEM_HOST) HIP_TRY(hipStreamSynchronize(s));
+    }
+    return FX_OK;
+}
+
+// The counts and the profile of a handle's searches.  cnt: [0] dropped
+// candidate ids, [1] queries flagged, [2] inverted files: coarse entries
+// outside the lists; copied stream-ordered into pin_cnt by a search and read
+// (after a synchronisation) when someone asks.  ev: `per_pass` events of every
+// profiled pass (4: start, prep, scan, refine + exact; inverted files 5:
+// start, coarse, pairs + prep, list scan, refine + exact).
+struct SearchStats {
+    DevArr<int> cnt;
+    PinArr<int> pin_cnt;
     bool counts_pending = false;
-    int64_t last_fallbacks = 0, last_dropped = 0;
-    int last_plan[4] = {0, 0, 0, 0};  // path, query tiles, splits, exact splits
-    int64_t last_qbatch = 0, last_grid = 0;
-    // profiling (fx_sq_profile): 4 events per pass -- start, after the query preparation, after the scan
-    // (exact path: the exact scan), after refine + exact fallback
+    int64_t last_fallbacks = 0, last_dropped = 0, last_bad_probe = 0;
     bool profile = false;
     std::vector<hipEvent_t> ev;
-    std::mutex mu;
-    hipStream_t stream() const { return user_stream ? user_stream : own_stream; }
+
+    hipError_t init_counts();
+    void clear_counts() {
+        counts_pending = false;
+        last_fallbacks = last_dropped = last_bad_probe = 0;
+    }
+    // a profiled pass's n events, the first recorded
+    hipError_t begin_pass(hipEvent_t* pass_ev, int n, hipStream_t s);
+    hipError_t mark(hipEvent_t e, hipStream_t s) { return profile ? hipEventRecord(e, s) : hipSuccess; }
+    void destroy_events();
+    // quant: the borrowed coarse quantizer, whose own integrity count is read with these
+    int read_counts(int device, hipStream_t s, FxIndex* quant = nullptr);
+    // ms[per_pass - 1] <- the summed parts of the passes since the last read
+    int profile_read(int device, hipStream_t s, int per_pass, double* const* ms, int64_t* passes);
 };
 
-// ---- fx_api_pq.cpp -------------------------------------------------------------
+struct Handle : SearchStats {
+    int device = 0;
+    hipStream_t own_stream = nullptr, user_stream = nullptr;
+    hipEvent_t switch_ev = nullptr;  // orders the work of a stream the index leaves before the next one's
+    Options opt;  // (force_fallback and the dump paths of the diagnostic build, read from the environment at creation)
+    std::mutex mu;
+    hipStream_t stream() const { return user_stream ? user_stream : own_stream; }
+    hipError_t init();  // the options, the stream, the event, the counts (the device current)
+};
+// the event hand-over of a stream switch, as fx_index_set_stream's
+int handle_set_stream(Handle* h, const char* kind, void* stream);
+
+// the calls every handle type H (a SearchStats with device, stream() and mu) answers alike
+template <class H>
+void handle_free(H* h) {
+    if (!h) return;
+    DeviceGuard g(h->device);
+    if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
+    if (h->user_stream) (void)hipStreamSynchronize(h->user_stream);
+    h->destroy_events();
+    if (h->switch_ev) (void)hipEventDestroy(h->switch_ev);
+    const hipStream_t own = h->own_stream;
+    delete h;  // its buffers, with the device current and before the stream goes
+    if (own) (void)hipStreamDestroy(own);
+}
+template <class H>
+int handle_profile(H* h, const char* kind, int enable) {
+    if (!h) return set_err(FX_E_ARG, "null %s index", kind);
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->profile = enable != 0;
+    return FX_OK;
+}
+template <class H, size_t N>
+int handle_profile_read(H* h, double* const (&ms)[N], int64_t* passes) {
+    if (!h) return set_err(FX_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    return h->profile_read(h->device, h->stream(), (int)N + 1, ms, passes);
+}
+// (a flagged query goes straight to the exact scan: both fallback counts are the same)
+template <class H>
+int handle_last_counts(H* h, FxIndex* quant, int64_t* fallbacks, int64_t* exact_fallbacks, int64_t* dropped) {
+    if (!h || !fallbacks || !exact_fallbacks || !dropped) return set_err(FX_E_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (const int rc = h->read_counts(h->device, h->stream(), quant); rc != FX_OK) return rc;
+    *fallbacks = h->last_fallbacks;
+    *exact_fallbacks = h->last_fallbacks;
+    *dropped = h->last_dropped + h->last_bad_probe;
+    return FX_OK;
+}
+
+// Codes [cap_rows][stride] and the rows' constants (n_c of the scalar
+// quantizers, n_y of the product quantizer), with a whole tile past the last
+// row; `lists`: the rows' labels and lists beside them (FxIvfSq).  Rows past
+// ntotal hold code 0 and constant 0: the scans mask them by row number.
+struct CodeRows {
+    int stride = 0;
+    int64_t ntotal = 0, cap_rows = 0;
+    bool lists = false;
+    DevArr<char> codes;
+    DevArr<float> nc;
+    DevArr<int64_t> labels;
+    DevArr<int> row_list;
+    // capacity for n rows (1.5x steps), the ntotal rows carried over; synchronises before the swap
+    hipError_t grow(int64_t n, hipStream_t s);
+    // codes and constants <- 0 (a reset)
+    hipError_t zero(hipStream_t s);
+};
+
+// What FxSq and FxPq share: the search driver's workspace and the last plan (fx_flat_codes.h)
+struct FlatCodes : Handle, CodeRows {
+    int d = 0, metric = L2;
+    bool trained = false;
+    // workspace of add / search / the codec
+    DevBuf in, qf32, planes, eps, rho, shift, cand_d, cand_i, flag, outD, outI, io;
+    int last_plan[4] = {0, 0, 0, 0};  // path, query tiles, splits, exact splits
+    int64_t last_qbatch = 0, last_grid = 0;
+};
+
+// The list state of an inverted file and its search workspace (fx_ivf_lists.h).
+// `quant` is the caller's coarse quantizer (borrowed).  row_list[r] is the list
+// of payload row r (nlist: an assignment outside the lists); the rows are in
+// list order once `dirty` is false.
+struct IvfLists {
+    FxIndex* quant = nullptr;
+    int64_t nlist = 0;
+    bool dirty = false;         // rows were appended since the last regroup
+    bool sequential = false;    // ids are ntotal .. (an add without ids); decided by the first add
+    int64_t max_list_rows = 0;  // of the last regroup
+    std::vector<int> h_off;     // list_off on the host, read back with it ([nlist + 1])
+    DevArr<int> list_off, max_rows;
+    DevBuf rws;                 // the regroup's sort workspace
+    DevBuf assign;              // a chunk's k = 1 search results
+    // search workspace
+    DevBuf qin, coarse_d, coarse_i, pkeys, psorted, seg, ngrp, gbase, ptemp, cand_d, cand_i, flag, outD, outI;
+    int last_plan[3] = {0, 0, 0};  // path, chunks, slots
+    int64_t last_qbatch = 0, last_grid = 0;
+};
+
+}  // namespace fx
+
+// An inverted-file index (include/fx_index.h, fx_ivf.hip).  `pay` is the payload
+// it owns: a labelled flat index, on whose stream and device everything runs.
+struct FxIvf : fx::SearchStats, fx::IvfLists {
+    FxIndex* pay = nullptr;
+    int device = 0;  // pay's
+    fx::DevArr<int> row_list;
+    fx::DevBuf ids;  // sequential ids of an add
+    fx::DevArr<unsigned long long> bad;  // assignments outside [0, nlist) since the last read
+    fx::QueryBufs qb;
+    std::mutex mu;
+    hipStream_t stream() const { return pay->stream(); }
+};
+
+// A scalar-quantizer index (include/fx_index.h, fx_sq.hip): 8-bit signed codes
+// (stride: the padded row), the rows' constants n_c, the trained tables
+// [vmin | vdiff] and the index-wide bound words.
+struct FxSq : fx::FlatCodes {
+    int qtype = 0;
+    bool train_open = false;  // fx_sq_train calls with more != 0 have accumulated min / max
+    fx::DevArr<float> tables;
+    fx::DevArr<unsigned> words, mm;
+    fx::DevArr<unsigned long long> bad;
+    fx::DevBuf sigma;
+};
 
 // A product quantizer index (include/fx_index.h "product quantizer", fx_pq.hip).  The fp32 centroids
 // are the truth; the scan image and the three constants of the bound are rebuilt from them on the
-// host whenever they are set.  Rows: stride = roundup(M, 16) code bytes and one fp32 n_y each.
-struct FxPq {
-    int d = 0, M = 0, dsub = 0, metric = fx::L2, device = 0, stride = 0, kp = 0;
-    int64_t ntotal = 0, cap_rows = 0;
-    bool trained = false;
+// host whenever they are set.  Rows: stride = roundup(M, 16) code bytes and one fp32 n_y (nc) each.
+struct FxPq : fx::FlatCodes {
+    int M = 0, dsub = 0, kp = 0;
     std::vector<float> h_cb;     // [M][256][dsub], the host copy fx_pq_get_centroids returns
     double Y = 0, Ry = 0, Yl = 0;  // max |decode|, max |y - y_hi - y_lo|, max |y_lo| over any code row
-    fx::DevArr<uint8_t> codes;
-    fx::DevArr<float> ny, cb;
+    fx::DevArr<float> cb;
     fx::DevArr<char> img;        // dsub % 8 == 0: [hi | lo] bf16 planes of pq_plane_bytes each
-    hipStream_t own_stream = nullptr, user_stream = nullptr;
-    hipEvent_t switch_ev = nullptr;
-    fx::Options opt;  // (force_fallback and the dump path of the diagnostic build, read at creation)
-    // workspace of add / search / the codec
-    fx::DevBuf in, qf32, planes, eps, rho, shift, cand_d, cand_i, flag, outD, outI, io;
-    fx::DevArr<int> cnt;  // [0] dropped candidate ids, [1] queries flagged
-    fx::PinArr<int> pin_cnt;
-    bool counts_pending = false;
-    int64_t last_fallbacks = 0, last_dropped = 0;
-    int last_plan[4] = {0, 0, 0, 0};  // path, query tiles, splits, exact splits
-    int64_t last_qbatch = 0, last_grid = 0;
-    // profiling (fx_pq_profile): 4 events per pass, as FxSq's
-    bool profile = false;
-    std::vector<hipEvent_t> ev;
-    std::mutex mu;
-    hipStream_t stream() const { return user_stream ? user_stream : own_stream; }
+    uint8_t* u8() const { return (uint8_t*)codes.p; }
 };
 
-// ---- fx_api_ivfsq.cpp ----------------------------------------------------------
-
-// An inverted file over 8-bit codes (include/fx_index.h, fx_ivfsq.hip).  `quant` is the caller's
-// coarse quantizer (borrowed).  The payload is FxSq's rows (signed codes with a whole tile past the
-// last row, n_c) with FxIvf's list state: labels, row_list (the rows' lists; nlist: an assignment
-// outside the lists), in list order once `dirty` is false.  cent holds the quantizer's centroids
-// widened to fp32 as they were when the tables were trained (by_residual only).
-struct FxIvfSq {
-    FxIndex* quant = nullptr;
-    int d = 0, qtype = 0, metric = fx::L2, device = 0, row_bytes = 0, by_residual = 1;
-    int64_t nlist = 0, ntotal = 0, cap_rows = 0;
+// An inverted file over 8-bit codes (include/fx_index.h, fx_ivfsq.hip).  The payload is FxSq's rows
+// with their labels and lists.  cent holds the quantizer's centroids widened to fp32 as they were
+// when the tables were trained (by_residual only).
+struct FxIvfSq : fx::Handle, fx::CodeRows, fx::IvfLists {
+    int d = 0, qtype = 0, metric = fx::L2, by_residual = 1;
     bool trained = false, train_open = false;
-    bool dirty = false, sequential = false;
-    int64_t max_list_rows = 0;
-    std::vector<int> h_off;
-    fx::DevArr<char> codes, codes_alt;
-    fx::DevArr<float> nc, nc_alt, tables, cent;
-    fx::DevArr<int64_t> labels, labels_alt;
-    fx::DevArr<int> row_list, row_list_alt, list_off, max_rows;
+    fx::DevArr<float> tables, cent;
     fx::DevArr<unsigned> words, mm;
     fx::DevArr<unsigned long long> bad;  // [0] non-finite training values, [1] assignments outside [0, nlist)
-    hipStream_t own_stream = nullptr, user_stream = nullptr;
-    hipEvent_t switch_ev = nullptr;
-    fx::Options opt;  // (force_fallback and the dump path of the diagnostic build, read at creation)
-    // workspace of train / add / the accessors
-    fx::DevBuf in, assign, tlist, resid, rws, io;
-    // search workspace
-    fx::DevBuf qin, qf32, planes, sigma, peps, pshift, coarse_d, coarse_i, pkeys, psorted, seg, ngrp, gbase, ptemp,
-        cand_d, cand_i, flag, outD, outI;
-    fx::DevArr<int> cnt;  // [0] dropped candidate ids, [1] queries flagged, [2] coarse entries outside the lists
-    fx::PinArr<int> pin_cnt;
-    bool counts_pending = false;
-    int64_t last_fallbacks = 0, last_dropped = 0, last_bad_probe = 0;
-    int last_plan[3] = {0, 0, 0};  // path, chunks, slots
-    int64_t last_qbatch = 0, last_grid = 0;
-    // profiling: 5 events per pass, as FxIvf's
-    bool profile = false;
-    std::vector<hipEvent_t> ev;
-    std::mutex mu;
-    hipStream_t stream() const { return user_stream ? user_stream : own_stream; }
+    // workspace of train / add / the accessors, and the search's pair operands
+    fx::DevBuf in, tlist, resid, io, qf32, planes, sigma, peps, pshift;
 };
 
 // A selector (include/fx_index.h): the device image fx_select.hip builds of a

@@ -76,14 +76,14 @@ hipError_t fx::blank_rows(FxIndex* h, int64_t r0, int64_t r1, hipStream_t s) {
     return e;
 }
 
-hipError_t fx::stage_in(FxIndex* h, DevBuf& buf, const void* src, size_t bytes, int mem, const void** dev,
+hipError_t fx::stage_in(hipStream_t s, DevBuf& buf, const void* src, size_t bytes, int mem, const void** dev,
                         size_t offset) {
     *dev = src;
     if (mem != FX_MEM_HOST) return hipSuccess;
-    hipError_t e = buf.ensure(offset + bytes);
+    hipError_t e = buf.ensure(std::max<size_t>(offset + bytes, 16));  // (never a null pointer for an empty input)
     if (e != hipSuccess) return e;
     *dev = (char*)buf.p + offset;
-    return hipMemcpyAsync((char*)buf.p + offset, src, bytes, hipMemcpyHostToDevice, h->stream());
+    return hipMemcpyAsync((char*)buf.p + offset, src, bytes, hipMemcpyHostToDevice, s);
 }
 
 extern "C" {

@@ -88,6 +88,46 @@ def _tensor_dtype(x) -> int:
 # ---------------------------------------------------------------------------
 # faiss IDSelector / SearchParameters (include/fx_index.h "filtered search")
 # ---------------------------------------------------------------------------
+def _out_arrays(x, nq: int, k: int, D, I) -> Tuple:
+    """``D`` and ``I`` of a search of the ``nq`` queries ``x``: allocated when
+    None, else the caller's, checked (the C side writes nq * k elements through
+    the raw pointer).  Device tensors on ``x``'s device when ``x`` is one, numpy
+    arrays otherwise."""
+    if _is_device_tensor(x):
+        t = _torch()
+        if D is None:
+            D = t.empty((nq, k), dtype=t.float32, device=x.device)
+        if I is None:
+            I = t.empty((nq, k), dtype=t.int64, device=x.device)
+        for name, a, dt in (("D", D, t.float32), ("I", I, t.int64)):
+            assert _is_device_tensor(a) and a.device == x.device, f"{name} must be on {x.device}"
+            assert a.dtype == dt and tuple(a.shape) == (nq, k) and a.is_contiguous(), \
+                f"{name} must be a contiguous {dt} tensor of shape ({nq}, {k})"
+        return D, I
+    D = np.empty((nq, k), dtype=np.float32) if D is None else D
+    I = np.empty((nq, k), dtype=np.int64) if I is None else I
+    for name, a, dt in (("D", D, np.float32), ("I", I, np.int64)):
+        assert isinstance(a, np.ndarray) and a.dtype == dt and a.shape == (nq, k) and \
+            a.flags.c_contiguous and a.flags.writeable, \
+            f"{name} must be a writeable C-contiguous {np.dtype(dt).name} array of shape ({nq}, {k})"
+    return D, I
+
+
+def _rows(self, x):
+    """(pointer, dtype code, mem, n, keep-alive) of the row input ``x`` of the
+    index ``self`` (whose stream is bound to match)."""
+    if _is_device_tensor(x):
+        assert x.dim() == 2 and x.shape[1] == self._d, "dimension mismatch"
+        assert x.device.index == self.device, f"tensor on cuda:{x.device.index}, index on cuda:{self.device}"
+        x = x.contiguous()
+        self._bind_stream(True)
+        return ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x), _lib.MEM_DEVICE, x.shape[0], x
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    assert x.ndim == 2 and x.shape[1] == self._d, "dimension mismatch"
+    self._bind_stream(False)
+    return x.ctypes.data_as(ctypes.c_void_p), _lib.F32, _lib.MEM_HOST, x.shape[0], x
+
+
 class IDSelector:
     """A set of ids a search is restricted to.  Ids are the ids ``search``
     returns (row + the index's id offset; on a labelled index -- ``IndexIDMap``
@@ -412,15 +452,7 @@ class _FlatIndex:
             assert x.device.index == self.device, f"queries on cuda:{x.device.index}, index on cuda:{self.device}"
             x = x.contiguous()
             nq = x.shape[0]
-            if D is None:
-                D = t.empty((nq, k), dtype=t.float32, device=x.device)
-            if I is None:
-                I = t.empty((nq, k), dtype=t.int64, device=x.device)
-            for name, a, dt in (("D", D, t.float32), ("I", I, t.int64)):
-                # the C side writes nq*k elements through the raw pointer
-                assert _is_device_tensor(a) and a.device == x.device, f"{name} must be on {x.device}"
-                assert a.dtype == dt and tuple(a.shape) == (nq, k) and a.is_contiguous(), \
-                    f"{name} must be a contiguous {dt} tensor of shape ({nq}, {k})"
+            D, I = _out_arrays(x, nq, k, D, I)
             self._bind_stream(True)
             if sel is not None:
                 self._check(self._lib.fx_index_search_sel(self._h, sel._handle(self), nq, ctypes.c_void_p(x.data_ptr()),
@@ -435,13 +467,7 @@ class _FlatIndex:
         x = np.ascontiguousarray(x, dtype=np.float32)
         assert x.ndim == 2 and x.shape[1] == self.d, "dimension mismatch"
         nq = x.shape[0]
-        Dh = np.empty((nq, k), dtype=np.float32) if D is None else D
-        Ih = np.empty((nq, k), dtype=np.int64) if I is None else I
-        for name, a, dt in (("D", Dh, np.float32), ("I", Ih, np.int64)):
-            # the C side writes nq*k elements through the raw pointer
-            assert isinstance(a, np.ndarray) and a.dtype == dt and a.shape == (nq, k) and \
-                a.flags.c_contiguous and a.flags.writeable, \
-                f"{name} must be a writeable C-contiguous {np.dtype(dt).name} array of shape ({nq}, {k})"
+        Dh, Ih = _out_arrays(x, nq, k, D, I)
         if sel is not None:
             # (a selector built from a device tensor is read on the stream that tensor was made on)
             self._bind_stream(_is_device_tensor(sel._spec()[1]))
@@ -1269,14 +1295,7 @@ class IndexIVFFlat:
             assert x.device.index == self.device, f"queries on cuda:{x.device.index}, index on cuda:{self.device}"
             x = x.contiguous()
             nq = x.shape[0]
-            if D is None:
-                D = t.empty((nq, k), dtype=t.float32, device=x.device)
-            if I is None:
-                I = t.empty((nq, k), dtype=t.int64, device=x.device)
-            for name, a, dt in (("D", D, t.float32), ("I", I, t.int64)):
-                assert _is_device_tensor(a) and a.device == x.device, f"{name} must be on {x.device}"
-                assert a.dtype == dt and tuple(a.shape) == (nq, k) and a.is_contiguous(), \
-                    f"{name} must be a contiguous {dt} tensor of shape ({nq}, {k})"
+            D, I = _out_arrays(x, nq, k, D, I)
             self._bind_stream(True)
             self._check(self._fn("search")(self._h, nq, ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x),
                                            _lib.MEM_DEVICE, k, nprobe, ctypes.c_void_p(D.data_ptr()),
@@ -1285,12 +1304,7 @@ class IndexIVFFlat:
         x = np.ascontiguousarray(x, dtype=np.float32)
         assert x.ndim == 2 and x.shape[1] == self._d, "dimension mismatch"
         nq = x.shape[0]
-        Dh = np.empty((nq, k), dtype=np.float32) if D is None else D
-        Ih = np.empty((nq, k), dtype=np.int64) if I is None else I
-        for name, a, dt in (("D", Dh, np.float32), ("I", Ih, np.int64)):
-            assert isinstance(a, np.ndarray) and a.dtype == dt and a.shape == (nq, k) and \
-                a.flags.c_contiguous and a.flags.writeable, \
-                f"{name} must be a writeable C-contiguous {np.dtype(dt).name} array of shape ({nq}, {k})"
+        Dh, Ih = _out_arrays(x, nq, k, D, I)
         self._bind_stream(False)
         self._check(self._fn("search")(self._h, nq, x.ctypes.data, _lib.F32, _lib.MEM_HOST, k, nprobe,
                                        Dh.ctypes.data, Ih.ctypes.data, _lib.MEM_HOST))
@@ -1378,7 +1392,216 @@ class ScalarQuantizer:
 _QT_NAMES = {v: k for k, v in vars(ScalarQuantizer).items() if k.startswith("QT_")}
 
 
-class IndexScalarQuantizer:
+class _CodeIndex:
+    """What ``IndexScalarQuantizer`` and ``IndexPQ`` share: a flat index of
+    8-bit codes behind the C entry points ``_PFX + name``, searched as its
+    decoded rows.  A subclass sets ``_PFX``, ``_CODE_DIM`` (the code width's
+    name in messages) and ``code_size``, names ``_last_plan`` as faiss-side
+    users know it, creates the handle and trains."""
+
+    _lib = lib
+    _PFX = _CODE_DIM = None
+
+    def _fn(self, name: str):
+        return getattr(self._lib, self._PFX + name)
+
+    def _check(self, rc: int) -> None:
+        check(rc, self._lib)
+
+    @property
+    def d(self) -> int:
+        return self._d
+
+    @property
+    def ntotal(self) -> int:
+        v = ctypes.c_int64(0)
+        self._check(self._fn("ntotal")(self._h, ctypes.byref(v)))
+        return v.value
+
+    @property
+    def is_trained(self) -> bool:
+        v = ctypes.c_int(0)
+        self._check(self._fn("is_trained")(self._h, ctypes.byref(v)))
+        return bool(v.value)
+
+    def _bind_stream(self, use_torch: bool) -> None:
+        s = _torch().cuda.current_stream(self.device).cuda_stream if use_torch else None
+        if getattr(self, "_bound", _UNBOUND) == s:
+            return
+        self._check(self._fn("set_stream")(self._h, ctypes.c_void_p(s) if s is not None else None))
+        self._bound = s
+
+    _rows = _rows
+
+    def _chunks_of(self, index):
+        """The stored rows of an unlabelled flat index of this module, chunk by
+        chunk as device tensors in its storage dtype (never through the host)."""
+        t = _torch()
+        flat = _flat(index)
+        assert not flat.has_ids and flat.device == self.device and flat.d == self._d
+        n = flat.ntotal
+        for r0 in range(0, n, KMEANS_CHUNK):
+            keys = t.arange(r0, min(n, r0 + KMEANS_CHUNK), dtype=t.int64, device=t.device("cuda", self.device))
+            yield flat.reconstruct_batch(keys + flat._id_offset, dtype="storage")
+
+    def add(self, x) -> None:
+        """Encode and append the rows of ``x`` with ids ``ntotal .. ntotal + n - 1``."""
+        assert self.is_trained, "the index is not trained"
+        ptr, code, mem, n, _keep = self._rows(x)
+        self._check(self._fn("add")(self._h, n, ptr, code, mem))
+
+    def add_from_index(self, index) -> None:
+        """Encode and append the stored rows of an unlabelled flat index of this
+        module in their order, gathered chunk by chunk on the device."""
+        for rows in self._chunks_of(index):
+            self.add(rows)
+
+    def search(self, x, k: int, *, params=None, D=None, I=None) -> Tuple:
+        """The k nearest decoded rows of every query.  numpy in -> numpy out
+        (blocks); device tensors in -> device tensors out, stream-ordered.
+        ``k <= 32`` takes the fused path (``IndexScalarQuantizer``: the int8
+        MFMA scan; ``IndexPQ``, with ``dsub % 8 == 0``: the gather scan on the
+        bf16 MFMA; then the exact refine), anything else the exact scan
+        (correct, one fp64 pass over every row); ``k > MAX_K``:
+        NotImplementedError."""
+        k = int(k)
+        if k <= 0:
+            raise AssertionError("k must be positive")
+        name = type(self).__name__
+        if params is not None and _selector_of(params) is not None:
+            raise NotImplementedError(f"{name}.search takes no selector")
+        assert self.is_trained, "the index is not trained"
+        if k > _lib.MAX_K:
+            raise NotImplementedError(f"{name}.search: k = {k} above MAX_K = {_lib.MAX_K}")
+        ptr, code, mem, nq, _keep = self._rows(x)
+        D, I = _out_arrays(x, nq, k, D, I)
+        if mem == _lib.MEM_DEVICE:
+            self._check(self._fn("search")(self._h, nq, ptr, code, mem, k, ctypes.c_void_p(D.data_ptr()),
+                                           ctypes.c_void_p(I.data_ptr()), mem))
+        else:
+            self._check(self._fn("search")(self._h, nq, ptr, code, mem, k, D.ctypes.data, I.ctypes.data, mem))
+        return D, I
+
+    def reconstruct_n(self, i0: int = 0, n: int = -1) -> np.ndarray:
+        """The decoded rows ``[i0, i0 + n)`` as numpy fp32 (n = -1: to the end)."""
+        i0 = int(i0)
+        n = self.ntotal - i0 if int(n) < 0 else int(n)
+        out = np.empty((n, self._d), dtype=np.float32)
+        self._bind_stream(False)
+        self._check(self._fn("reconstruct_n")(self._h, i0, n, out.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST))
+        return out
+
+    def reconstruct_batch(self, keys):
+        """The decoded rows of ``keys``: numpy in -> numpy fp32 out (a key
+        outside the index raises); an int64 device tensor in -> a device tensor
+        out, stream-ordered (a key outside the index gives a NaN row)."""
+        if _is_device_tensor(keys):
+            t = _torch()
+            keys = keys.to(t.int64).contiguous().reshape(-1)
+            out = t.empty((int(keys.numel()), self._d), dtype=t.float32, device=keys.device)
+            self._bind_stream(True)
+            self._check(self._fn("reconstruct_batch")(self._h, int(keys.numel()), ctypes.c_void_p(keys.data_ptr()),
+                                                      _lib.MEM_DEVICE, ctypes.c_void_p(out.data_ptr()), _lib.MEM_DEVICE))
+            return out
+        keys = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        n = self.ntotal
+        if keys.size and (keys.min() < 0 or keys.max() >= n):
+            raise RuntimeError(f"reconstruct_batch: a key outside [0, {n})")
+        out = np.empty((int(keys.size), self._d), dtype=np.float32)
+        self._bind_stream(False)
+        self._check(self._fn("reconstruct_batch")(self._h, int(keys.size), ctypes.c_void_p(keys.ctypes.data),
+                                                  _lib.MEM_HOST, ctypes.c_void_p(out.ctypes.data), _lib.MEM_HOST))
+        return out
+
+    def reconstruct(self, key: int) -> np.ndarray:
+        return self.reconstruct_batch(np.array([int(key)], dtype=np.int64))[0]
+
+    def sa_encode(self, x):
+        """Rows -> faiss's codes ``(n, code_size)`` uint8 (a scalar quantizer's
+        are unsigned; numpy in -> numpy out; a device tensor in -> a device
+        tensor out)."""
+        ptr, code, mem, n, _keep = self._rows(x)
+        if mem == _lib.MEM_DEVICE:
+            t = _torch()
+            out = t.empty((n, self.code_size), dtype=t.uint8, device=_keep.device)
+            self._check(self._fn("encode")(self._h, n, ptr, code, ctypes.c_void_p(out.data_ptr()), mem))
+            return out
+        out = np.empty((n, self.code_size), dtype=np.uint8)
+        self._check(self._fn("encode")(self._h, n, ptr, code, ctypes.c_void_p(out.ctypes.data), mem))
+        return out
+
+    def sa_decode(self, codes):
+        """faiss's codes ``(n, code_size)`` uint8 -> fp32 rows."""
+        cs, what = self.code_size, f"codes must be (n, {self._CODE_DIM}) uint8"
+        if _is_device_tensor(codes):
+            t = _torch()
+            assert codes.dtype == t.uint8 and codes.dim() == 2 and codes.shape[1] == cs, what
+            codes = codes.contiguous()
+            out = t.empty((codes.shape[0], self._d), dtype=t.float32, device=codes.device)
+            self._bind_stream(True)
+            self._check(self._fn("decode")(self._h, codes.shape[0], ctypes.c_void_p(codes.data_ptr()),
+                                           ctypes.c_void_p(out.data_ptr()), _lib.MEM_DEVICE))
+            return out
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        assert codes.ndim == 2 and codes.shape[1] == cs, what
+        out = np.empty((codes.shape[0], self._d), dtype=np.float32)
+        self._bind_stream(False)
+        self._check(self._fn("decode")(self._h, codes.shape[0], ctypes.c_void_p(codes.ctypes.data),
+                                       ctypes.c_void_p(out.ctypes.data), _lib.MEM_HOST))
+        return out
+
+    def reset(self) -> None:
+        """Empties the index; the training stays, as in faiss."""
+        self._check(self._fn("reset")(self._h))
+
+    def _counts(self):
+        a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._fn("last_counts")(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+    def last_fallbacks(self) -> int:
+        return self._counts()[0]
+
+    def last_exact_fallbacks(self) -> int:
+        return self._counts()[1]
+
+    def last_dropped_candidates(self) -> int:
+        return self._counts()[2]
+
+    def _last_plan(self) -> dict:
+        """The planner's outputs for the last search: ``path`` ("fused" /
+        "exact"), ``qtiles`` per pass, corpus ``splits`` per query tile,
+        ``xsplits`` of the exact scan, ``q_batch``, ``grid``."""
+        p, t_, s, x = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        qb, g = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._fn("last_plan")(self._h, ctypes.byref(p), ctypes.byref(t_), ctypes.byref(s),
+                                          ctypes.byref(x), ctypes.byref(qb), ctypes.byref(g)))
+        return {"path": "exact" if p.value else "fused", "qtiles": t_.value, "splits": s.value, "xsplits": x.value,
+                "q_batch": qb.value, "grid": g.value}
+
+    def profile(self, enable: bool = True) -> None:
+        """Record HIP events around the parts of every search pass."""
+        self._check(self._fn("profile")(self._h, 1 if enable else 0))
+
+    def profile_read(self) -> dict:
+        """Milliseconds since the last read (waits for the stream): ``prep``,
+        ``scan``, ``refine`` (+ exact fallback), and the ``passes`` they cover."""
+        ms = [ctypes.c_double(0) for _ in range(3)]
+        n = ctypes.c_int64(0)
+        self._check(self._fn("profile_read")(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(n)))
+        return {"prep": ms[0].value, "scan": ms[1].value, "refine": ms[2].value, "passes": n.value}
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                self._fn("free")(h)
+            except Exception:  # noqa: BLE001 - interpreter shutdown
+                pass
+            self._h = None
+
+
+class IndexScalarQuantizer(_CodeIndex):
     """``faiss.IndexScalarQuantizer(d, qtype, metric)`` with 8-bit codes: one
     byte per dimension after a per-dimension (``QT_8bit``) or global
     (``QT_8bit_uniform``) affine quantisation trained as min / max.  A search
@@ -1392,7 +1615,7 @@ class IndexScalarQuantizer:
     ``remove_ids``, ``range_search``, ``IndexIDMap`` over it, ``write_index``
     / ``read_index``."""
 
-    _lib = lib
+    _PFX, _CODE_DIM = "fx_sq_", "d"
 
     def __init__(self, d: int, qtype: int = ScalarQuantizer.QT_8bit, metric: int = METRIC_L2, device: int = 0):
         qtype = int(qtype)
@@ -1407,61 +1630,11 @@ class IndexScalarQuantizer:
         self._d, self.qtype, self.metric_type, self.device = int(d), qtype, int(metric), int(device)
         self._lib = self._lib  # the build this handle belongs to, for its whole life
         self._h = ctypes.c_void_p()
-        self._check(self._lib.fx_sq_create(self._d, qtype, self.metric_type, self.device, ctypes.byref(self._h)))
-
-    def _check(self, rc: int) -> None:
-        check(rc, self._lib)
-
-    @property
-    def d(self) -> int:
-        return self._d
+        self._check(self._fn("create")(self._d, qtype, self.metric_type, self.device, ctypes.byref(self._h)))
 
     @property
     def code_size(self) -> int:
         return self._d
-
-    @property
-    def ntotal(self) -> int:
-        v = ctypes.c_int64(0)
-        self._check(self._lib.fx_sq_ntotal(self._h, ctypes.byref(v)))
-        return v.value
-
-    @property
-    def is_trained(self) -> bool:
-        v = ctypes.c_int(0)
-        self._check(self._lib.fx_sq_is_trained(self._h, ctypes.byref(v)))
-        return bool(v.value)
-
-    def _bind_stream(self, use_torch: bool) -> None:
-        s = _torch().cuda.current_stream(self.device).cuda_stream if use_torch else None
-        if getattr(self, "_bound", _UNBOUND) == s:
-            return
-        self._check(self._lib.fx_sq_set_stream(self._h, ctypes.c_void_p(s) if s is not None else None))
-        self._bound = s
-
-    def _rows(self, x):
-        """(pointer, dtype code, mem, n, keep-alive) of row input ``x``."""
-        if _is_device_tensor(x):
-            assert x.dim() == 2 and x.shape[1] == self._d, "dimension mismatch"
-            assert x.device.index == self.device, f"tensor on cuda:{x.device.index}, index on cuda:{self.device}"
-            x = x.contiguous()
-            self._bind_stream(True)
-            return ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x), _lib.MEM_DEVICE, x.shape[0], x
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        assert x.ndim == 2 and x.shape[1] == self._d, "dimension mismatch"
-        self._bind_stream(False)
-        return x.ctypes.data_as(ctypes.c_void_p), _lib.F32, _lib.MEM_HOST, x.shape[0], x
-
-    def _chunks_of(self, index):
-        """The stored rows of an unlabelled flat index of this module, chunk by
-        chunk as device tensors in its storage dtype (never through the host)."""
-        t = _torch()
-        flat = _flat(index)
-        assert not flat.has_ids and flat.device == self.device and flat.d == self._d
-        n = flat.ntotal
-        for r0 in range(0, n, KMEANS_CHUNK):
-            keys = t.arange(r0, min(n, r0 + KMEANS_CHUNK), dtype=t.int64, device=t.device("cuda", self.device))
-            yield flat.reconstruct_batch(keys + flat._id_offset, dtype="storage")
 
     def train(self, x) -> None:
         """Per-dimension (``QT_8bit_uniform``: global) min and max of ``x``:
@@ -1472,18 +1645,18 @@ class IndexScalarQuantizer:
         if _is_index(x):
             for rows in self._chunks_of(x):
                 ptr, code, mem, n, _keep = self._rows(rows)
-                self._check(self._lib.fx_sq_train(self._h, n, ptr, code, mem, 1))
-            self._check(self._lib.fx_sq_train(self._h, 0, None, _lib.F32, _lib.MEM_DEVICE, 0))
+                self._check(self._fn("train")(self._h, n, ptr, code, mem, 1))
+            self._check(self._fn("train")(self._h, 0, None, _lib.F32, _lib.MEM_DEVICE, 0))
             return
         ptr, code, mem, n, _keep = self._rows(x)
-        self._check(self._lib.fx_sq_train(self._h, n, ptr, code, mem, 0))
+        self._check(self._fn("train")(self._h, n, ptr, code, mem, 0))
 
     @property
     def trained(self) -> np.ndarray:
         """faiss's ``sq.trained``: ``[vmin[d] | vdiff[d]]`` fp32 (``QT_8bit_uniform``:
         ``[vmin, vdiff]``)."""
         out = np.empty(2 * self._d, dtype=np.float32)
-        self._check(self._lib.fx_sq_get_trained(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        self._check(self._fn("get_trained")(self._h, out.ctypes.data_as(ctypes.c_void_p)))
         if self.qtype == ScalarQuantizer.QT_8bit_uniform:
             return np.array([out[0], out[self._d]], dtype=np.float32)
         return out
@@ -1495,175 +1668,9 @@ class IndexScalarQuantizer:
         if self.qtype == ScalarQuantizer.QT_8bit_uniform and a.size == 2:
             a = np.concatenate([np.full(self._d, a[0], np.float32), np.full(self._d, a[1], np.float32)])
         assert a.size == 2 * self._d, f"trained must hold {2 * self._d} floats"
-        self._check(self._lib.fx_sq_set_trained(self._h, a.ctypes.data_as(ctypes.c_void_p)))
+        self._check(self._fn("set_trained")(self._h, a.ctypes.data_as(ctypes.c_void_p)))
 
-    def add(self, x) -> None:
-        """Append the rows of ``x`` with ids ``ntotal .. ntotal + n - 1``."""
-        assert self.is_trained, "the index is not trained"
-        ptr, code, mem, n, _keep = self._rows(x)
-        self._check(self._lib.fx_sq_add(self._h, n, ptr, code, mem))
-
-    def add_from_index(self, index) -> None:
-        """Append the stored rows of an unlabelled flat index of this module in
-        their order, gathered chunk by chunk on the device."""
-        for rows in self._chunks_of(index):
-            self.add(rows)
-
-    def search(self, x, k: int, *, params=None, D=None, I=None) -> Tuple:
-        """The k nearest decoded rows of every query.  numpy in -> numpy out
-        (blocks); device tensors in -> device tensors out, stream-ordered.
-        ``k <= 32`` takes the fused path (int8 MFMA scan + exact refine),
-        larger k the exact scan (correct, one fp64 pass over every row);
-        ``k > MAX_K``: NotImplementedError."""
-        k = int(k)
-        if k <= 0:
-            raise AssertionError("k must be positive")
-        if params is not None and _selector_of(params) is not None:
-            raise NotImplementedError("IndexScalarQuantizer.search takes no selector")
-        assert self.is_trained, "the index is not trained"
-        if k > _lib.MAX_K:
-            raise NotImplementedError(f"IndexScalarQuantizer.search: k = {k} above MAX_K = {_lib.MAX_K}")
-        if _is_device_tensor(x):
-            t = _torch()
-            ptr, code, mem, nq, _keep = self._rows(x)
-            if D is None:
-                D = t.empty((nq, k), dtype=t.float32, device=x.device)
-            if I is None:
-                I = t.empty((nq, k), dtype=t.int64, device=x.device)
-            for name, a, dt in (("D", D, t.float32), ("I", I, t.int64)):
-                assert _is_device_tensor(a) and a.device == x.device, f"{name} must be on {x.device}"
-                assert a.dtype == dt and tuple(a.shape) == (nq, k) and a.is_contiguous(), \
-                    f"{name} must be a contiguous {dt} tensor of shape ({nq}, {k})"
-            self._check(self._lib.fx_sq_search(self._h, nq, ptr, code, mem, k, ctypes.c_void_p(D.data_ptr()),
-                                               ctypes.c_void_p(I.data_ptr()), _lib.MEM_DEVICE))
-            return D, I
-        ptr, code, mem, nq, _keep = self._rows(x)
-        Dh = np.empty((nq, k), dtype=np.float32) if D is None else D
-        Ih = np.empty((nq, k), dtype=np.int64) if I is None else I
-        for name, a, dt in (("D", Dh, np.float32), ("I", Ih, np.int64)):
-            assert isinstance(a, np.ndarray) and a.dtype == dt and a.shape == (nq, k) and \
-                a.flags.c_contiguous and a.flags.writeable, \
-                f"{name} must be a writeable C-contiguous {np.dtype(dt).name} array of shape ({nq}, {k})"
-        self._check(self._lib.fx_sq_search(self._h, nq, ptr, code, mem, k, Dh.ctypes.data, Ih.ctypes.data,
-                                           _lib.MEM_HOST))
-        return Dh, Ih
-
-    def reconstruct_n(self, i0: int = 0, n: int = -1) -> np.ndarray:
-        """The decoded rows ``[i0, i0 + n)`` as numpy fp32 (n = -1: to the end)."""
-        i0 = int(i0)
-        n = self.ntotal - i0 if int(n) < 0 else int(n)
-        out = np.empty((n, self._d), dtype=np.float32)
-        self._bind_stream(False)
-        self._check(self._lib.fx_sq_reconstruct_n(self._h, i0, n, out.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST))
-        return out
-
-    def reconstruct_batch(self, keys):
-        """The decoded rows of ``keys``: numpy in -> numpy fp32 out (a key
-        outside the index raises); an int64 device tensor in -> a device tensor
-        out, stream-ordered (a key outside the index gives a NaN row)."""
-        if _is_device_tensor(keys):
-            t = _torch()
-            keys = keys.to(t.int64).contiguous().reshape(-1)
-            out = t.empty((int(keys.numel()), self._d), dtype=t.float32, device=keys.device)
-            self._bind_stream(True)
-            self._check(self._lib.fx_sq_reconstruct_batch(self._h, int(keys.numel()), ctypes.c_void_p(keys.data_ptr()),
-                                                          _lib.MEM_DEVICE, ctypes.c_void_p(out.data_ptr()),
-                                                          _lib.MEM_DEVICE))
-            return out
-        keys = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
-        n = self.ntotal
-        if keys.size and (keys.min() < 0 or keys.max() >= n):
-            raise RuntimeError(f"reconstruct_batch: a key outside [0, {n})")
-        out = np.empty((int(keys.size), self._d), dtype=np.float32)
-        self._bind_stream(False)
-        self._check(self._lib.fx_sq_reconstruct_batch(self._h, int(keys.size), ctypes.c_void_p(keys.ctypes.data),
-                                                      _lib.MEM_HOST, ctypes.c_void_p(out.ctypes.data), _lib.MEM_HOST))
-        return out
-
-    def reconstruct(self, key: int) -> np.ndarray:
-        return self.reconstruct_batch(np.array([int(key)], dtype=np.int64))[0]
-
-    def sa_encode(self, x):
-        """Rows -> faiss's unsigned codes ``(n, d)`` uint8 (numpy in -> numpy
-        out; a device tensor in -> a device tensor out)."""
-        ptr, code, mem, n, _keep = self._rows(x)
-        if mem == _lib.MEM_DEVICE:
-            t = _torch()
-            out = t.empty((n, self._d), dtype=t.uint8, device=_keep.device)
-            self._check(self._lib.fx_sq_encode(self._h, n, ptr, code, ctypes.c_void_p(out.data_ptr()), mem))
-            return out
-        out = np.empty((n, self._d), dtype=np.uint8)
-        self._check(self._lib.fx_sq_encode(self._h, n, ptr, code, ctypes.c_void_p(out.ctypes.data), mem))
-        return out
-
-    def sa_decode(self, codes):
-        """faiss's unsigned codes ``(n, d)`` -> fp32 rows."""
-        if _is_device_tensor(codes):
-            t = _torch()
-            assert codes.dtype == t.uint8 and codes.dim() == 2 and codes.shape[1] == self._d, "codes must be (n, d) uint8"
-            codes = codes.contiguous()
-            out = t.empty((codes.shape[0], self._d), dtype=t.float32, device=codes.device)
-            self._bind_stream(True)
-            self._check(self._lib.fx_sq_decode(self._h, codes.shape[0], ctypes.c_void_p(codes.data_ptr()),
-                                               ctypes.c_void_p(out.data_ptr()), _lib.MEM_DEVICE))
-            return out
-        codes = np.ascontiguousarray(codes, dtype=np.uint8)
-        assert codes.ndim == 2 and codes.shape[1] == self._d, "codes must be (n, d) uint8"
-        out = np.empty((codes.shape[0], self._d), dtype=np.float32)
-        self._bind_stream(False)
-        self._check(self._lib.fx_sq_decode(self._h, codes.shape[0], ctypes.c_void_p(codes.ctypes.data),
-                                           ctypes.c_void_p(out.ctypes.data), _lib.MEM_HOST))
-        return out
-
-    def reset(self) -> None:
-        """Empties the index; the training stays, as in faiss."""
-        self._check(self._lib.fx_sq_reset(self._h))
-
-    def _counts(self):
-        a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-        self._check(self._lib.fx_sq_last_counts(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
-        return a.value, b.value, c.value
-
-    def last_fallbacks(self) -> int:
-        return self._counts()[0]
-
-    def last_exact_fallbacks(self) -> int:
-        return self._counts()[1]
-
-    def last_dropped_candidates(self) -> int:
-        return self._counts()[2]
-
-    def last_sq_plan(self) -> dict:
-        """The planner's outputs for the last search: ``path`` ("fused" /
-        "exact"), ``qtiles`` per pass, corpus ``splits`` per query tile,
-        ``xsplits`` of the exact scan, ``q_batch``, ``grid``."""
-        p, t_, s, x = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-        qb, g = ctypes.c_int64(0), ctypes.c_int64(0)
-        self._check(self._lib.fx_sq_last_plan(self._h, ctypes.byref(p), ctypes.byref(t_), ctypes.byref(s),
-                                              ctypes.byref(x), ctypes.byref(qb), ctypes.byref(g)))
-        return {"path": "exact" if p.value else "fused", "qtiles": t_.value, "splits": s.value, "xsplits": x.value,
-                "q_batch": qb.value, "grid": g.value}
-
-    def profile(self, enable: bool = True) -> None:
-        """Record HIP events around the parts of every search pass."""
-        self._check(self._lib.fx_sq_profile(self._h, 1 if enable else 0))
-
-    def profile_read(self) -> dict:
-        """Milliseconds since the last read (waits for the stream): ``prep``,
-        ``scan``, ``refine`` (+ exact fallback), and the ``passes`` they cover."""
-        ms = [ctypes.c_double(0) for _ in range(3)]
-        n = ctypes.c_int64(0)
-        self._check(self._lib.fx_sq_profile_read(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(n)))
-        return {"prep": ms[0].value, "scan": ms[1].value, "refine": ms[2].value, "passes": n.value}
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                self._lib.fx_sq_free(h)
-            except Exception:  # noqa: BLE001 - interpreter shutdown
-                pass
-            self._h = None
+    last_sq_plan = _CodeIndex._last_plan
 
 
 # ---------------------------------------------------------------------------
@@ -1699,7 +1706,7 @@ class ProductQuantizer:
         ix._check(ix._lib.fx_pq_set_centroids(ix._h, a.ctypes.data_as(ctypes.c_void_p)))
 
 
-class IndexPQ:
+class IndexPQ(_CodeIndex):
     """``faiss.IndexPQ(d, M, nbits, metric)`` with 8-bit codes: M bytes per row,
     byte m naming one of the 256 centroids of sub-quantizer m; a row decodes to
     the concatenation of its centroids (``reconstruct``, bitwise).  A search
@@ -1713,7 +1720,7 @@ class IndexPQ:
     ``remove_ids``, ``range_search``, ``IndexIDMap`` over it, ``write_index`` /
     ``read_index``."""
 
-    _lib = lib
+    _PFX, _CODE_DIM = "fx_pq_", "M"
 
     def __init__(self, d: int, M: int, nbits: int = 8, metric: int = METRIC_L2, device: int = 0, niter: int = 25,
                  seed: int = 1234):
@@ -1727,40 +1734,11 @@ class IndexPQ:
         self.pq = ProductQuantizer(self, d, M, nbits, niter, seed)
         self._lib = self._lib  # the build this handle belongs to, for its whole life
         self._h = ctypes.c_void_p()
-        self._check(self._lib.fx_pq_create(d, M, nbits, self.metric_type, self.device, ctypes.byref(self._h)))
-
-    def _check(self, rc: int) -> None:
-        check(rc, self._lib)
-
-    @property
-    def d(self) -> int:
-        return self._d
+        self._check(self._fn("create")(d, M, nbits, self.metric_type, self.device, ctypes.byref(self._h)))
 
     @property
     def code_size(self) -> int:
         return self.pq.M
-
-    @property
-    def ntotal(self) -> int:
-        v = ctypes.c_int64(0)
-        self._check(self._lib.fx_pq_ntotal(self._h, ctypes.byref(v)))
-        return v.value
-
-    @property
-    def is_trained(self) -> bool:
-        v = ctypes.c_int(0)
-        self._check(self._lib.fx_pq_is_trained(self._h, ctypes.byref(v)))
-        return bool(v.value)
-
-    def _bind_stream(self, use_torch: bool) -> None:
-        s = _torch().cuda.current_stream(self.device).cuda_stream if use_torch else None
-        if getattr(self, "_bound", _UNBOUND) == s:
-            return
-        self._check(self._lib.fx_pq_set_stream(self._h, ctypes.c_void_p(s) if s is not None else None))
-        self._bound = s
-
-    _rows = IndexScalarQuantizer._rows
-    _chunks_of = IndexScalarQuantizer._chunks_of
 
     def train(self, x) -> None:
         """``Kmeans(dsub, 256, niter=pq.niter, seed=pq.seed)`` on the contiguous
@@ -1800,133 +1778,13 @@ class IndexPQ:
             cents[m] = km.centroids
         pq.centroids = cents
 
-    def add(self, x) -> None:
-        """Encode and append the rows of ``x`` with ids ``ntotal .. ntotal + n - 1``."""
-        assert self.is_trained, "the index is not trained"
-        ptr, code, mem, n, _keep = self._rows(x)
-        self._check(self._lib.fx_pq_add(self._h, n, ptr, code, mem))
-
-    def add_from_index(self, index) -> None:
-        """Encode and append the stored rows of an unlabelled flat index of this
-        module in their order, gathered chunk by chunk on the device."""
-        for rows in self._chunks_of(index):
-            self.add(rows)
-
-    def search(self, x, k: int, *, params=None, D=None, I=None) -> Tuple:
-        """The k nearest decoded rows of every query.  numpy in -> numpy out
-        (blocks); device tensors in -> device tensors out, stream-ordered.
-        ``k <= 32`` with ``dsub % 8 == 0`` takes the fused path (the gather scan
-        on the bf16 MFMA + exact refine), anything else the exact scan (correct,
-        one fp64 pass over every row); ``k > MAX_K``: NotImplementedError."""
-        k = int(k)
-        if k <= 0:
-            raise AssertionError("k must be positive")
-        if params is not None and _selector_of(params) is not None:
-            raise NotImplementedError("IndexPQ.search takes no selector")
-        assert self.is_trained, "the index is not trained"
-        if k > _lib.MAX_K:
-            raise NotImplementedError(f"IndexPQ.search: k = {k} above MAX_K = {_lib.MAX_K}")
-        if _is_device_tensor(x):
-            t = _torch()
-            ptr, code, mem, nq, _keep = self._rows(x)
-            if D is None:
-                D = t.empty((nq, k), dtype=t.float32, device=x.device)
-            if I is None:
-                I = t.empty((nq, k), dtype=t.int64, device=x.device)
-            for name, a, dt in (("D", D, t.float32), ("I", I, t.int64)):
-                assert _is_device_tensor(a) and a.device == x.device, f"{name} must be on {x.device}"
-                assert a.dtype == dt and tuple(a.shape) == (nq, k) and a.is_contiguous(), \
-                    f"{name} must be a contiguous {dt} tensor of shape ({nq}, {k})"
-            self._check(self._lib.fx_pq_search(self._h, nq, ptr, code, mem, k, ctypes.c_void_p(D.data_ptr()),
-                                               ctypes.c_void_p(I.data_ptr()), _lib.MEM_DEVICE))
-            return D, I
-        ptr, code, mem, nq, _keep = self._rows(x)
-        Dh = np.empty((nq, k), dtype=np.float32) if D is None else D
-        Ih = np.empty((nq, k), dtype=np.int64) if I is None else I
-        for name, a, dt in (("D", Dh, np.float32), ("I", Ih, np.int64)):
-            assert isinstance(a, np.ndarray) and a.dtype == dt and a.shape == (nq, k) and \
-                a.flags.c_contiguous and a.flags.writeable, \
-                f"{name} must be a writeable C-contiguous {np.dtype(dt).name} array of shape ({nq}, {k})"
-        self._check(self._lib.fx_pq_search(self._h, nq, ptr, code, mem, k, Dh.ctypes.data, Ih.ctypes.data,
-                                           _lib.MEM_HOST))
-        return Dh, Ih
-
-    def reconstruct_n(self, i0: int = 0, n: int = -1) -> np.ndarray:
-        """The decoded rows ``[i0, i0 + n)`` as numpy fp32 (n = -1: to the end)."""
-        i0 = int(i0)
-        n = self.ntotal - i0 if int(n) < 0 else int(n)
-        out = np.empty((n, self._d), dtype=np.float32)
-        self._bind_stream(False)
-        self._check(self._lib.fx_pq_reconstruct_n(self._h, i0, n, out.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST))
-        return out
-
-    def reconstruct_batch(self, keys):
-        """The decoded rows of ``keys``: numpy in -> numpy fp32 out (a key
-        outside the index raises); an int64 device tensor in -> a device tensor
-        out, stream-ordered (a key outside the index gives a NaN row)."""
-        if _is_device_tensor(keys):
-            t = _torch()
-            keys = keys.to(t.int64).contiguous().reshape(-1)
-            out = t.empty((int(keys.numel()), self._d), dtype=t.float32, device=keys.device)
-            self._bind_stream(True)
-            self._check(self._lib.fx_pq_reconstruct_batch(self._h, int(keys.numel()), ctypes.c_void_p(keys.data_ptr()),
-                                                          _lib.MEM_DEVICE, ctypes.c_void_p(out.data_ptr()),
-                                                          _lib.MEM_DEVICE))
-            return out
-        keys = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
-        n = self.ntotal
-        if keys.size and (keys.min() < 0 or keys.max() >= n):
-            raise RuntimeError(f"reconstruct_batch: a key outside [0, {n})")
-        out = np.empty((int(keys.size), self._d), dtype=np.float32)
-        self._bind_stream(False)
-        self._check(self._lib.fx_pq_reconstruct_batch(self._h, int(keys.size), ctypes.c_void_p(keys.ctypes.data),
-                                                      _lib.MEM_HOST, ctypes.c_void_p(out.ctypes.data), _lib.MEM_HOST))
-        return out
-
-    def reconstruct(self, key: int) -> np.ndarray:
-        return self.reconstruct_batch(np.array([int(key)], dtype=np.int64))[0]
-
-    def sa_encode(self, x):
-        """Rows -> codes ``(n, M)`` uint8 (numpy in -> numpy out; a device
-        tensor in -> a device tensor out)."""
-        ptr, code, mem, n, _keep = self._rows(x)
-        M = self.pq.M
-        if mem == _lib.MEM_DEVICE:
-            t = _torch()
-            out = t.empty((n, M), dtype=t.uint8, device=_keep.device)
-            self._check(self._lib.fx_pq_encode(self._h, n, ptr, code, ctypes.c_void_p(out.data_ptr()), mem))
-            return out
-        out = np.empty((n, M), dtype=np.uint8)
-        self._check(self._lib.fx_pq_encode(self._h, n, ptr, code, ctypes.c_void_p(out.ctypes.data), mem))
-        return out
-
-    def sa_decode(self, codes):
-        """Codes ``(n, M)`` uint8 -> fp32 rows."""
-        M = self.pq.M
-        if _is_device_tensor(codes):
-            t = _torch()
-            assert codes.dtype == t.uint8 and codes.dim() == 2 and codes.shape[1] == M, "codes must be (n, M) uint8"
-            codes = codes.contiguous()
-            out = t.empty((codes.shape[0], self._d), dtype=t.float32, device=codes.device)
-            self._bind_stream(True)
-            self._check(self._lib.fx_pq_decode(self._h, codes.shape[0], ctypes.c_void_p(codes.data_ptr()),
-                                               ctypes.c_void_p(out.data_ptr()), _lib.MEM_DEVICE))
-            return out
-        codes = np.ascontiguousarray(codes, dtype=np.uint8)
-        assert codes.ndim == 2 and codes.shape[1] == M, "codes must be (n, M) uint8"
-        out = np.empty((codes.shape[0], self._d), dtype=np.float32)
-        self._bind_stream(False)
-        self._check(self._lib.fx_pq_decode(self._h, codes.shape[0], ctypes.c_void_p(codes.ctypes.data),
-                                           ctypes.c_void_p(out.ctypes.data), _lib.MEM_HOST))
-        return out
-
     def get_codes(self, i0: int = 0, n: int = -1) -> np.ndarray:
         """The codes of the rows ``[i0, i0 + n)`` as numpy ``(n, M)`` uint8 (n = -1: to the end)."""
         i0 = int(i0)
         n = self.ntotal - i0 if int(n) < 0 else int(n)
         out = np.empty((n, self.pq.M), dtype=np.uint8)
         self._bind_stream(False)
-        self._check(self._lib.fx_pq_get_codes(self._h, i0, n, ctypes.c_void_p(out.ctypes.data), _lib.MEM_HOST))
+        self._check(self._fn("get_codes")(self._h, i0, n, ctypes.c_void_p(out.ctypes.data), _lib.MEM_HOST))
         return out
 
     @property
@@ -1934,55 +1792,7 @@ class IndexPQ:
         """faiss's ``index.codes``: every row's code, ``(ntotal, M)`` uint8."""
         return self.get_codes()
 
-    def reset(self) -> None:
-        """Empties the index; the centroids stay, as in faiss."""
-        self._check(self._lib.fx_pq_reset(self._h))
-
-    def _counts(self):
-        a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-        self._check(self._lib.fx_pq_last_counts(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
-        return a.value, b.value, c.value
-
-    def last_fallbacks(self) -> int:
-        return self._counts()[0]
-
-    def last_exact_fallbacks(self) -> int:
-        return self._counts()[1]
-
-    def last_dropped_candidates(self) -> int:
-        return self._counts()[2]
-
-    def last_pq_plan(self) -> dict:
-        """The planner's outputs for the last search: ``path`` ("fused" /
-        "exact"), ``qtiles`` per pass, corpus ``splits`` per query tile,
-        ``xsplits`` of the exact scan, ``q_batch``, ``grid``."""
-        p, t_, s, x = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-        qb, g = ctypes.c_int64(0), ctypes.c_int64(0)
-        self._check(self._lib.fx_pq_last_plan(self._h, ctypes.byref(p), ctypes.byref(t_), ctypes.byref(s),
-                                              ctypes.byref(x), ctypes.byref(qb), ctypes.byref(g)))
-        return {"path": "exact" if p.value else "fused", "qtiles": t_.value, "splits": s.value, "xsplits": x.value,
-                "q_batch": qb.value, "grid": g.value}
-
-    def profile(self, enable: bool = True) -> None:
-        """Record HIP events around the parts of every search pass."""
-        self._check(self._lib.fx_pq_profile(self._h, 1 if enable else 0))
-
-    def profile_read(self) -> dict:
-        """Milliseconds since the last read (waits for the stream): ``prep``,
-        ``scan``, ``refine`` (+ exact fallback), and the ``passes`` they cover."""
-        ms = [ctypes.c_double(0) for _ in range(3)]
-        n = ctypes.c_int64(0)
-        self._check(self._lib.fx_pq_profile_read(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(n)))
-        return {"prep": ms[0].value, "scan": ms[1].value, "refine": ms[2].value, "passes": n.value}
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                self._lib.fx_pq_free(h)
-            except Exception:  # noqa: BLE001 - interpreter shutdown
-                pass
-            self._h = None
+    last_pq_plan = _CodeIndex._last_plan
 
 
 # ---------------------------------------------------------------------------
@@ -2046,18 +1856,7 @@ class IndexIVFScalarQuantizer(IndexIVFFlat):
         self._check(self._fn("is_trained")(self._h, ctypes.byref(v)))
         return bool(v.value)
 
-    def _rows(self, x):
-        """(pointer, dtype code, mem, n, keep-alive) of row input ``x``."""
-        if _is_device_tensor(x):
-            assert x.dim() == 2 and x.shape[1] == self._d, "dimension mismatch"
-            assert x.device.index == self.device, f"tensor on cuda:{x.device.index}, index on cuda:{self.device}"
-            x = x.contiguous()
-            self._bind_stream(True)
-            return ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x), _lib.MEM_DEVICE, x.shape[0], x
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        assert x.ndim == 2 and x.shape[1] == self._d, "dimension mismatch"
-        self._bind_stream(False)
-        return x.ctypes.data_as(ctypes.c_void_p), _lib.F32, _lib.MEM_HOST, x.shape[0], x
+    _rows = _rows
 
     def train(self, x) -> None:
         """k-means on the quantizer if it holds no centroids yet (as
