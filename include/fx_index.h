@@ -580,8 +580,9 @@ int fx_kmeans_profile_read(FxIndex* centroids, double* assign_ms, double* sort_m
  * Out of scope: writing / reading an IVF index (faiss's "IwFl" layout cannot
  * be checked here: persist the quantizer as IxF2 and re-add the rows),
  * remove_ids, range_search, selectors, reconstruct*, search_preassigned,
- * sharding across GPUs, the search graph, IndexIVFPQ (8-bit lists:
- * "inverted file over 8-bit codes" below). */
+ * sharding across GPUs, the search graph (8-bit lists: "inverted file over
+ * 8-bit codes" below; product-quantized lists: "inverted file over
+ * product-quantized codes"). */
 typedef struct FxIvf FxIvf;
 int fx_ivf_create(FxIndex* quantizer, int d, int64_t nlist, int storage_dtype, int metric, FxIvf** out);
 void fx_ivf_free(FxIvf* ivf);
@@ -774,7 +775,7 @@ int fx_sq_profile_read(FxSq* sq, double* prep_ms, double* scan_ms, double* refin
  * FX_MAX_K and ntotal >= 2^31; FX_E_INTEGRITY as the scalar quantizer's.  nq ==
  * 0 and n == 0 are FX_OK.
  *
- * Out of scope: IndexIVFPQ, nbits != 8, fast-scan 4-bit codes, OPQ, polysemous
+ * Out of scope: nbits != 8, fast-scan 4-bit codes, OPQ, polysemous
  * and symmetric (SDC) search, selectors, remove_ids, range_search, IndexIDMap
  * over it, write_index / read_index, sharding and the search graph. */
 typedef struct FxPq FxPq;
@@ -866,7 +867,7 @@ int fx_pq_profile_read(FxPq* pq, double* prep_ms, double* scan_ms, double* refin
  *
  * Out of scope: write_index / read_index (faiss's "IwSQ" layout cannot be checked
  * here), remove_ids, range_search, selectors, reconstruct* by id, sharding, the
- * search graph, the other qtypes, IndexIVFPQ. */
+ * search graph, the other qtypes. */
 typedef struct FxIvfSq FxIvfSq;
 int fx_ivfsq_create(FxIndex* quantizer, int d, int64_t nlist, int qtype, int metric, int by_residual, FxIvfSq** out);
 void fx_ivfsq_free(FxIvfSq* ivfsq);
@@ -902,6 +903,104 @@ int fx_ivfsq_last_counts(FxIvfSq* ivfsq, int64_t* fallbacks, int64_t* exact_fall
 int fx_ivfsq_last_plan(FxIvfSq* ivfsq, int* path, int* chunks, int* slots, int64_t* q_batch, int64_t* grid);
 int fx_ivfsq_profile(FxIvfSq* ivfsq, int enable);
 int fx_ivfsq_profile_read(FxIvfSq* ivfsq, double* coarse_ms, double* pairs_ms, double* scan_ms, double* refine_ms,
+                          int64_t* passes);
+
+/* ---- inverted file over product-quantized codes: faiss IndexIVFPQ (8-bit) ------
+ *
+ *   faiss (Python)                               faiss C++ / C API                          this ABI
+ *   IndexIVFPQ(quantizer, d, nlist, M, nbits,    faiss_IndexIVFPQ_new_with_metric           fx_ivfpq_create
+ *       metric); index.by_residual
+ *   index.train(x)                               faiss_Index_train                          the k-means calls above and fx_index_add
+ *                                                                                           on the quantizer, fx_ivfpq_residuals, M
+ *                                                                                           k-means runs, fx_ivfpq_set_centroids
+ *   index.is_trained                             faiss_Index_is_trained                     fx_ivfpq_is_trained (and the quantizer's rows)
+ *   index.pq.centroids                           ProductQuantizer::centroids                fx_ivfpq_get_centroids / _set_centroids
+ *   quantizer.compute_residual_n                 Index::compute_residual_n                  fx_ivfpq_residuals
+ *   index.add(x) / add_with_ids(x, ids)          faiss_Index_add / _add_with_ids            fx_ivfpq_add
+ *   index.nprobe; index.search(x, k)             faiss_IndexIVF_set_nprobe / _Index_search  fx_ivfpq_search
+ *   index.reset()                                faiss_Index_reset                          fx_ivfpq_reset
+ *   index.ntotal                                 faiss_Index_ntotal                         fx_ivfpq_ntotal
+ *   invlists.list_size(l) / get_ids(l)           faiss_IndexIVF_get_list_size / ..get_ids   fx_ivfpq_list_sizes / _list_ids
+ *   invlists.get_codes(l)                        InvertedLists::get_codes                   fx_ivfpq_list_codes
+ *   (GC of the index)                            faiss_Index_free                           fx_ivfpq_free
+ *
+ * Like the sections it joins ("inverted file", "product quantizer"), this
+ * restates faiss from memory and is NOT checked against a faiss build.  The
+ * deliberate difference the section above names holds here too: faiss ranks a
+ * row of list l by the distance between the query's residual and the decoded
+ * residual (through its distance tables), this contract by the decoded row.
+ *
+ * Lists.  The quantizer, a row's list, the regroup after an add, the ids
+ * (sequential or the caller's int64, never mixed), the probe set
+ * quantizer.search(q, min(nprobe, nlist)) and the missing slots I = -1, D =
+ * +-FLT_MAX: all exactly as the "inverted file" section says.
+ *
+ * Encoded vector.  With by_residual != 0 (faiss's default) the encoded vector of
+ * a row of list l is r = fl32(x - c_l), one rounded fp32 subtraction per
+ * dimension against the fp32 centroid the quantizer reconstructs (as it was when
+ * the codebook was set); otherwise r = x.  The code is the "product quantizer"
+ * section's encode(r), bitwise: fp64 argmin, dimensions ascending, no
+ * contraction, the lowest j on a tie.
+ *
+ * Decoded row.  y = fl32(c_l + decode(code)), or decode(code) without
+ * by_residual: the gather is bitwise and the addition is rounded once.
+ *
+ * Search.  Per query the k rows of its probed lists that minimise sum (x_j -
+ * y_j)^2 (L2) or maximise sum x_j y_j (IP) over the decoded fp32 y, the sum in
+ * fp64 rounded once to fp32, ranked by (that value, list number, insertion order
+ * within the list).  k <= 32 and dsub % 8 == 0: the fused path (operand
+ * preparation per (query, probe) pair, the gather list scan on the bf16 MFMA,
+ * exact refine + certification, the exact list scan for uncertified queries, all
+ * decided on the device).  32 < k <= FX_MAX_K, and every index whose dsub is no
+ * multiple of 8: the exact list scan for the whole search (one fp64 pass over the
+ * decoded rows of the probed lists: correct, slow).  fx_ivfpq_last_plan reports
+ * which path ran.
+ *
+ * Errors: those of fx_ivf_* and fx_pq_*, with the same limits.  FX_E_ARG also for
+ * set_centroids while the quantizer does not hold nlist centroids or the index
+ * holds rows, and for add or search before the codebook is set;
+ * FX_E_UNSUPPORTED for nbits != 8.
+ *
+ * Out of scope: precomputed tables, polysemous search, nbits != 8, OPQ, fast-scan,
+ * write_index / read_index, remove_ids, range_search, selectors, reconstruct* by
+ * id, sharding, the search graph. */
+typedef struct FxIvfPq FxIvfPq;
+int fx_ivfpq_create(FxIndex* quantizer, int d, int64_t nlist, int M, int nbits, int metric, int by_residual,
+                    FxIvfPq** out);
+void fx_ivfpq_free(FxIvfPq* ivfpq);
+int fx_ivfpq_is_trained(const FxIvfPq* ivfpq, int* out);
+/* out / centroids: host [M][256][dsub] floats.  Setting them (a trained
+ * quantizer, an index without rows) reads the quantizer's centroids, rebuilds
+ * the scan image and marks the index trained. */
+int fx_ivfpq_get_centroids(FxIvfPq* ivfpq, float* out);
+int fx_ivfpq_set_centroids(FxIvfPq* ivfpq, const float* centroids);
+/* faiss's compute_residual_n: out [n][d] fp32 (out_mem) <- fl32(x_i - c_l), l the
+ * list of row i (the quantizer's k = 1 search); a copy of x widened to fp32
+ * without by_residual.  What the codebook is trained on. */
+int fx_ivfpq_residuals(FxIvfPq* ivfpq, int64_t n, const void* x, int x_dtype, int x_mem, float* out, int out_mem);
+/* ids NULL: sequential ids ntotal .. ntotal + n - 1.  Device x (and ids) is
+ * stream-ordered; host x blocks. */
+int fx_ivfpq_add(FxIvfPq* ivfpq, int64_t n, const void* x, int x_dtype, int x_mem, const int64_t* ids, int ids_mem);
+/* Host results block; device queries and results are stream-ordered (the first
+ * search after an add synchronises once for the regroup). */
+int fx_ivfpq_search(FxIvfPq* ivfpq, int64_t nq, const void* q, int q_dtype, int q_mem, int k, int nprobe, float* D,
+                    int64_t* I, int out_mem);
+/* Empties the lists; the quantizer and the codebook stay. */
+int fx_ivfpq_reset(FxIvfPq* ivfpq);
+int fx_ivfpq_ntotal(const FxIvfPq* ivfpq, int64_t* out);
+/* out: host [nlist]. */
+int fx_ivfpq_list_sizes(FxIvfPq* ivfpq, int64_t* out);
+/* *n = rows of `list`; out (host, cap entries; may be NULL with cap 0) receives
+ * the first min(*n, cap) ids / code rows in insertion order.  Codes are faiss's
+ * [.][M] uint8. */
+int fx_ivfpq_list_ids(FxIvfPq* ivfpq, int64_t list, int64_t* out, int64_t cap, int64_t* n);
+int fx_ivfpq_list_codes(FxIvfPq* ivfpq, int64_t list, uint8_t* out, int64_t cap, int64_t* n);
+int fx_ivfpq_set_stream(FxIvfPq* ivfpq, void* stream);
+/* As fx_ivfsq_last_counts / _last_plan / _profile / _profile_read. */
+int fx_ivfpq_last_counts(FxIvfPq* ivfpq, int64_t* fallbacks, int64_t* exact_fallbacks, int64_t* dropped);
+int fx_ivfpq_last_plan(FxIvfPq* ivfpq, int* path, int* chunks, int* slots, int64_t* q_batch, int64_t* grid);
+int fx_ivfpq_profile(FxIvfPq* ivfpq, int enable);
+int fx_ivfpq_profile_read(FxIvfPq* ivfpq, double* coarse_ms, double* pairs_ms, double* scan_ms, double* refine_ms,
                           int64_t* passes);
 
 /* faiss.write_index / faiss.read_index on the IxF2 format (faiss_store.py:

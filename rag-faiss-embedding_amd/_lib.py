@@ -155,6 +155,25 @@ SIGNATURES = {
                                 ctypes.POINTER(_i64)]),
     "fx_ivfsq_profile": (_i, [_vp, _i]),
     "fx_ivfsq_profile_read": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(_i64)]),
+    "fx_ivfpq_create": (_i, [_vp, _i, _i64, _i, _i, _i, _i, _pp]),
+    "fx_ivfpq_free": (None, [_vp]),
+    "fx_ivfpq_is_trained": (_i, [_vp, ctypes.POINTER(_i)]),
+    "fx_ivfpq_get_centroids": (_i, [_vp, _vp]),
+    "fx_ivfpq_set_centroids": (_i, [_vp, _vp]),
+    "fx_ivfpq_residuals": (_i, [_vp, _i64, _vp, _i, _i, _vp, _i]),
+    "fx_ivfpq_add": (_i, [_vp, _i64, _vp, _i, _i, _vp, _i]),
+    "fx_ivfpq_search": (_i, [_vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _i]),
+    "fx_ivfpq_reset": (_i, [_vp]),
+    "fx_ivfpq_ntotal": (_i, [_vp, ctypes.POINTER(_i64)]),
+    "fx_ivfpq_list_sizes": (_i, [_vp, _vp]),
+    "fx_ivfpq_list_ids": (_i, [_vp, _i64, _vp, _i64, ctypes.POINTER(_i64)]),
+    "fx_ivfpq_list_codes": (_i, [_vp, _i64, _vp, _i64, ctypes.POINTER(_i64)]),
+    "fx_ivfpq_set_stream": (_i, [_vp, _vp]),
+    "fx_ivfpq_last_counts": (_i, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "fx_ivfpq_last_plan": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64),
+                                ctypes.POINTER(_i64)]),
+    "fx_ivfpq_profile": (_i, [_vp, _i]),
+    "fx_ivfpq_profile_read": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(_i64)]),
     "fx_index_write": (_i, [_vp, ctypes.c_char_p]),
     "fx_index_read": (_i, [ctypes.c_char_p, _i, _i, _pp]),
     "fx_merge_shards": (_i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -144,6 +144,57 @@ struct PqOps {
 
 }  // namespace
 
+namespace fx {
+
+int pq_codebook(const char* kind, int M, int dsub, const float* centroids, PqCodebook& out) {
+    const size_t nval = (size_t)M * PQ_KSUB * dsub;
+    for (size_t i = 0; i < nval; ++i)
+        if (!std::isfinite(centroids[i]))
+            return set_err(FX_E_ARG, "%s set_centroids: centroid %lld of sub-quantizer %lld has a non-finite value", kind,
+                           (long long)(i / dsub % PQ_KSUB), (long long)(i / dsub / PQ_KSUB));
+    // the bound's constants: per sub-quantizer maxima, so they hold for any code row; the scan image
+    const bool scan = dsub % 8 == 0;
+    const size_t plane = (size_t)pq_plane_bytes(M, dsub) / 2;  // bf16 values of a plane
+    out.img.assign(scan ? 2 * plane : 0, 0);
+    double y2 = 0.0, r2 = 0.0, l2 = 0.0;
+    for (int m = 0; m < M; ++m) {
+        double my = 0.0, mr = 0.0, ml = 0.0;
+        for (int j = 0; j < PQ_KSUB; ++j) {
+            double sy = 0.0, sr = 0.0, sl = 0.0;
+            for (int e = 0; e < dsub; ++e) {
+                const size_t i = ((size_t)m * PQ_KSUB + j) * dsub + e;
+                const float v = centroids[i];
+                const uint16_t hb = host_f2bf(v);
+                const float rest = v - host_bf2f(hb);  // exact in fp32
+                const uint16_t lb = std::isfinite(host_bf2f(hb)) ? host_f2bf(rest) : (uint16_t)0;
+                const double lo = (double)host_bf2f(lb), res = (double)rest - lo;
+                sy += (double)v * (double)v;
+                sr += res * res;
+                sl += lo * lo;
+                if (scan) {
+                    out.img[i] = hb;
+                    out.img[plane + i] = lb;
+                }
+            }
+            my = std::max(my, sy);
+            mr = std::max(mr, sr);
+            ml = std::max(ml, sl);
+        }
+        y2 += my;
+        r2 += mr;
+        l2 += ml;
+    }
+    if (!std::isfinite(y2) || !std::isfinite(r2) || !(y2 < 1e37))
+        return set_err(FX_E_ARG, "%s set_centroids: the centroids' norms leave the fp32 range", kind);
+    const double up = 1.0 + 1e-9;
+    out.Y = std::sqrt(y2) * up;
+    out.Ry = std::sqrt(r2) * up;
+    out.Yl = std::sqrt(l2) * up;
+    return FX_OK;
+}
+
+}  // namespace fx
+
 extern "C" {
 
 int fx_pq_create(int d, int M, int nbits, int metric, int device, FxPq** out) {
@@ -199,58 +250,20 @@ int fx_pq_set_centroids(FxPq* h, const float* centroids) {
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->ntotal > 0)
         return set_err(FX_E_ARG, "pq set_centroids: the index holds %lld rows (reset it first)", (long long)h->ntotal);
-    const int M = h->M, dsub = h->dsub;
-    const size_t nval = (size_t)M * PQ_KSUB * dsub;
-    for (size_t i = 0; i < nval; ++i)
-        if (!std::isfinite(centroids[i]))
-            return set_err(FX_E_ARG, "pq set_centroids: centroid %lld of sub-quantizer %lld has a non-finite value",
-                           (long long)(i / dsub % PQ_KSUB), (long long)(i / dsub / PQ_KSUB));
-    // the bound's constants: per sub-quantizer maxima, so they hold for any code row; the scan image
-    const bool scan = dsub % 8 == 0;
-    const size_t plane = (size_t)pq_plane_bytes(M, dsub) / 2;  // bf16 values of a plane
-    std::vector<uint16_t> img(scan ? 2 * plane : 0, 0);
-    double y2 = 0.0, r2 = 0.0, l2 = 0.0;
-    for (int m = 0; m < M; ++m) {
-        double my = 0.0, mr = 0.0, ml = 0.0;
-        for (int j = 0; j < PQ_KSUB; ++j) {
-            double sy = 0.0, sr = 0.0, sl = 0.0;
-            for (int e = 0; e < dsub; ++e) {
-                const size_t i = ((size_t)m * PQ_KSUB + j) * dsub + e;
-                const float v = centroids[i];
-                const uint16_t hb = host_f2bf(v);
-                const float rest = v - host_bf2f(hb);  // exact in fp32
-                const uint16_t lb = std::isfinite(host_bf2f(hb)) ? host_f2bf(rest) : (uint16_t)0;
-                const double lo = (double)host_bf2f(lb), res = (double)rest - lo;
-                sy += (double)v * (double)v;
-                sr += res * res;
-                sl += lo * lo;
-                if (scan) {
-                    img[i] = hb;
-                    img[plane + i] = lb;
-                }
-            }
-            my = std::max(my, sy);
-            mr = std::max(mr, sr);
-            ml = std::max(ml, sl);
-        }
-        y2 += my;
-        r2 += mr;
-        l2 += ml;
-    }
-    if (!std::isfinite(y2) || !std::isfinite(r2) || !(y2 < 1e37))
-        return set_err(FX_E_ARG, "pq set_centroids: the centroids' norms leave the fp32 range");
+    const size_t nval = (size_t)h->M * PQ_KSUB * h->dsub;
+    PqCodebook cbk;
+    if (const int rc = pq_codebook("pq", h->M, h->dsub, centroids, cbk); rc != FX_OK) return rc;
     DeviceGuard g(h->device);
     if (!g.ok) return set_err(FX_E_HIP, "hipSetDevice(%d) failed", h->device);
     hipStream_t s = h->stream();
     HIP_TRY(hipStreamSynchronize(s));  // (an earlier search may still read the image)
     HIP_TRY(hipMemcpyAsync(h->cb, centroids, nval * 4, hipMemcpyHostToDevice, s));
-    if (scan) HIP_TRY(hipMemcpyAsync(h->img, img.data(), img.size() * 2, hipMemcpyHostToDevice, s));
+    if (!cbk.img.empty()) HIP_TRY(hipMemcpyAsync(h->img, cbk.img.data(), cbk.img.size() * 2, hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));
     h->h_cb.assign(centroids, centroids + nval);
-    const double up = 1.0 + 1e-9;
-    h->Y = std::sqrt(y2) * up;
-    h->Ry = std::sqrt(r2) * up;
-    h->Yl = std::sqrt(l2) * up;
+    h->Y = cbk.Y;
+    h->Ry = cbk.Ry;
+    h->Yl = cbk.Yl;
     h->trained = true;
     return FX_OK;
 }

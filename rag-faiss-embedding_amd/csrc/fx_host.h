@@ -189,6 +189,7 @@ struct Options {
     std::string sq_cand, ivf_cand;  // FX_SQ_CAND / FX_IVF_CAND: the scan lists of fx_sq_search / fx_ivf_search, per pass
     std::string ivfsq_cand;         // FX_IVFSQ_CAND: the scan lists and pair operands of fx_ivfsq_search, per pass
     std::string pq_cand;            // FX_PQ_CAND: the scan lists, query operands and row constants of fx_pq_search, per pass
+    std::string ivfpq_cand;         // FX_IVFPQ_CAND: the scan lists, pair operands and rows of fx_ivfpq_search, per pass
 #else
     static constexpr int force_fallback = 0, scan_dbg = 0;
 #endif
@@ -239,6 +240,7 @@ struct Options {
         str("FX_IVF_CAND", ivf_cand);
         str("FX_IVFSQ_CAND", ivfsq_cand);
         str("FX_PQ_CAND", pq_cand);
+        str("FX_IVFPQ_CAND", ivfpq_cand);
 #endif
     }
     // option name -> its slot and accepted range [lo, hi] (allowed: a value
@@ -572,9 +574,10 @@ struct BorrowQuant {
 
 // ---- fx_api_handle.cpp: what the indexes beside the flat one share -------------
 //
-// FxSq, FxPq and FxIvfSq are a Handle (stream, options, lock, counts, profile)
-// over CodeRows (their payload); FxSq and FxPq share FlatCodes and its search
-// driver (fx_flat_codes.h); FxIvf and FxIvfSq share IvfLists (fx_ivf_lists.h).
+// FxSq, FxPq, FxIvfSq and FxIvfPq are a Handle (stream, options, lock, counts,
+// profile) over CodeRows (their payload); FxSq and FxPq share FlatCodes and its
+// search driver (fx_flat_codes.h); FxIvf, FxIvfSq and FxIvfPq share IvfLists
+// (fx_ivf_lists.h).
 
 namespace fx {
 
@@ -591,6 +594,15 @@ int need_trained(bool trained, const char* kind, const char* call);
 int check_rows(int64_t n, int x_dtype, int x_mem);
 // a trained table [vmin | vdiff] as the scalar quantizers accept it
 int sq_check_tables(const char* kind, int d, const float* trained);
+// What a product quantizer derives from its centroids [M][256][dsub] on the host (fx_api_pq.cpp): the
+// scan image (dsub % 8 == 0: two bf16 planes [hi | lo] of pq_plane_bytes each, else empty) and the
+// bound's constants max |decode|, max |y - y_hi - y_lo|, max |y_lo| over any code row.  FX_E_ARG for a
+// non-finite centroid or norms outside the fp32 range.
+struct PqCodebook {
+    std::vector<uint16_t> img;
+    double Y = 0, Ry = 0, Yl = 0;
+};
+int pq_codebook(const char* kind, int M, int dsub, const float* centroids, PqCodebook& out);
 
 // Rows x [n][d] through the bounded staging buffer `in` (<= 256 MiB a chunk, or
 // `chunk` rows): body(xd, r0, nr) per chunk, and one synchronisation per chunk
@@ -787,6 +799,23 @@ struct FxIvfSq : fx::Handle, fx::CodeRows, fx::IvfLists {
     fx::DevArr<unsigned long long> bad;  // [0] non-finite training values, [1] assignments outside [0, nlist)
     // workspace of train / add / the accessors, and the search's pair operands
     fx::DevBuf in, tlist, resid, io, qf32, planes, sigma, peps, pshift;
+};
+
+// An inverted file over product-quantized codes (include/fx_index.h, fx_ivfpq.hip).  The payload is
+// FxPq's rows with their labels and lists; the codebook, its scan image and constants are FxPq's.
+// cent holds the quantizer's centroids widened to fp32 as they were when the codebook was set
+// (by_residual only), rho_dec the rounding bound of fl32(c_l + decode) they give.
+struct FxIvfPq : fx::Handle, fx::CodeRows, fx::IvfLists {
+    int d = 0, M = 0, dsub = 0, kp = 0, metric = fx::L2, by_residual = 1;
+    bool trained = false;
+    std::vector<float> h_cb;     // [M][256][dsub], the host copy fx_ivfpq_get_centroids returns
+    double Y = 0, Ry = 0, Yl = 0, rho_dec = 0;
+    fx::DevArr<float> cb, cent;
+    fx::DevArr<char> img;        // dsub % 8 == 0: [hi | lo] bf16 planes of pq_plane_bytes each
+    fx::DevArr<unsigned long long> bad;  // [1] assignments outside [0, nlist) ([0] unused, as FxIvfSq's layout)
+    // workspace of add / residuals / the accessors, and the search's operands
+    fx::DevBuf in, tlist, resid, io, qf32, planes, peps, pshift;
+    uint8_t* u8() const { return (uint8_t*)codes.p; }
 };
 
 // A selector (include/fx_index.h): the device image fx_select.hip builds of a

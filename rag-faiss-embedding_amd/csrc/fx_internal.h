@@ -1,5 +1,5 @@
 // fx_internal.h -- shared between the HIP translation units (fx_kernels.hip,
-// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip, fx_kmeans.hip, fx_ivf.hip, fx_sq.hip, fx_ivfsq.hip, fx_pq.hip) and the host C ABI
+// fx_scan.hip, fx_scan5.hip, fx_hugek.hip, fx_range.hip, fx_select.hip, fx_remove.hip, fx_idmap.hip, fx_recon.hip, fx_kmeans.hip, fx_ivf.hip, fx_sq.hip, fx_ivfsq.hip, fx_pq.hip, fx_ivfpq.hip) and the host C ABI
 // (fx_index.cpp, fx_api_*.cpp, fx_plan.cpp; their own header: fx_host.h):
 // tiling constants, kernel parameter blocks, the launchers' prototypes and
 // their host-side helpers.  Not part of the public ABI (include/fx_index.h).
@@ -835,6 +835,84 @@ struct PqExact {
     int64_t* I;
 };
 hipError_t launch_pq_exact(int metric, const PqExact& p, hipStream_t s);
+// inverted file over product-quantized codes (fx_ivfpq.hip): faiss's IndexIVFPQ with 8-bit codes.  The
+// payload is the inverted file's (list order, list_off, row_list) with the product quantizer's rows
+// (pq_stride(M) code bytes, n_y = |decode|^2); with by_residual a code encodes fl32(x - c_l) and the row
+// decodes to fl32(c_l + decode(code)).  cent is the fp32 centroids [nlist][d], or null without by_residual.
+// Operand preparation.  per_pair != 0 (L2 with by_residual): operand row = pair p = q * np + j, x' = -2
+// fl32(x - c_l), shift |x - c_l|^2.  Otherwise the operand row = the query (IP: -x; L2 without
+// by_residual: -2 x) and only shift (IP: -(x . c_l); else |x|^2 / 0) and E are per pair.
+struct IvfPqPrep {
+    const void* q;          // [nq][d] on the device
+    int q_dt, metric, d, kp;
+    int64_t nq;
+    int np, per_pair;
+    int64_t op_rows;        // plane rows: >= nq * np (per_pair) or >= nq; rows past the live ones are zero operands
+    const int64_t* coarse;  // [nq][np] probed lists
+    int64_t nlist;
+    const float* cent;      // [nlist][d] or null
+    double Y, Ry, Yl, rho_dec;  // FxPq's constants, and the rounding bound of fl32(c_l + decode) (0 without by_residual)
+    float* qf32;            // [nq][kp] fp32 queries, zero padded
+    uint16_t* planes;       // [2][op_rows][kp] bf16 hi / lo
+    float* peps;            // [nq * np] E of the pair
+    float* pshift;          // [nq * np] fl32(shift)
+    int* zero[2];           // counters set to 0
+};
+hipError_t launch_ivfpq_prep(const IvfPqPrep& p, hipStream_t s);
+// k_ivfpq_scan: k_ivfsq_scan's grid and list logic around k_pq_scan's gather tile loop; the B planes
+// are fetched by operand row pair / bdiv.  key = fl(fl(n_y + S) + shift) (IP: fl(S + shift)).
+struct IvfPqScan {
+    const uint8_t* codes; // [rows][stride] in list order, a whole zero tile past the last row
+    const float* ny;
+    int stride, M, dsub, d, kp;
+    const char* img;      // the codebook's scan image
+    int64_t plane_bytes;
+    const int* list_off;
+    int64_t nlist;
+    const uint16_t* planes;  // [2][op_rows][kp]
+    int64_t op_rows;
+    int bdiv;             // operand row of pair p: p / bdiv (1: per pair; np: per query)
+    const float* pshift;  // [nq * np]
+    int np, C;
+    const uint64_t* sorted;
+    const int* seg;
+    const int* gbase;
+    float* cand_d;        // [nq][np * C][KP]
+    int* cand_i;
+    int64_t grid;
+};
+hipError_t launch_ivfpq_scan(int metric, const IvfPqScan& p, hipStream_t s);
+// k_ivfsq_refine's three phases; the exact recomputation gathers the fp32 centroids and adds the list's
+struct IvfPqRefine {
+    const float* cand_d;
+    const int* cand_i;
+    int slots, np;
+    int64_t nq, ntotal;
+    int k, d, kp, dsub, stride;
+    const uint8_t* codes;
+    const float* cb;        // [M][256][dsub]
+    const int* row_list;    // [ntotal] the rows' lists
+    int64_t nlist;
+    const float* cent;      // or null
+    double rho_dec;
+    const float* qf32;      // [nq][kp]
+    const float* peps;      // [nq * np]
+    const int64_t* labels;
+    float* D;
+    int64_t* I;
+    int* n_flag;
+    int* n_drop;
+    int force_fb;
+};
+hipError_t launch_ivfpq_refine(int metric, const IvfPqRefine& p, hipStream_t s);
+// k_ivfpq_exact (k_ivf_exact over decoded rows: gather plus centroid) + k_ivf_merge
+struct IvfPqExact {
+    IvfExact ex;            // codes: the code bytes; row_bytes: their stride; kdim: the fp32 queries' stride (kp)
+    int d, dsub;
+    const float* cb;
+    const float* cent;      // or null
+};
+hipError_t launch_ivfpq_exact(int metric, const IvfPqExact& p, hipStream_t s);
 hipError_t launch_synth(void* out, int64_t row0, int64_t n, int d, int dtype, uint64_t seed,
                         hipStream_t s);
 hipError_t launch_to_f32(const void* codes, int st_dt, int row_bytes, int64_t n, int d, float* out,

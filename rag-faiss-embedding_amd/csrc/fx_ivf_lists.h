@@ -1,4 +1,4 @@
-// fx_ivf_lists.h -- what the two inverted files (FxIvf, FxIvfSq) share beyond the handle core: the regroup
+// fx_ivf_lists.h -- what the inverted files (FxIvf, FxIvfSq, FxIvfPq) share beyond the handle core: the regroup
 // into list order, the rules of an add, the coarse / pairs steps and the ends of a search, the list
 // accessors (fx_api_ivf.cpp defines them).  The list scan, refine and exact steps are each file's own.
 #pragma once

@@ -53,16 +53,6 @@ unsigned ivfsq_grid(int64_t items, int per_block) {
 
 }  // namespace
 
-// one rounded fp32 addition / subtraction that no neighbouring multiply is fused into
-__device__ __forceinline__ float add_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ float sub_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-
 // ---------------------------------------------------------------------------
 // residuals, constants, list codes
 // ---------------------------------------------------------------------------

@@ -282,6 +282,33 @@ SqPlan plan_pq(int64_t nq, int64_t ntotal, int k, int M, int dsub) {
     return sq_exact_plan(std::max<int64_t>(nq, 1), xs, k);
 }
 
+IvfPqPlan plan_ivfpq(int64_t nq, int nprobe_eff, int64_t nlist, int64_t max_list_rows, int64_t ntotal, int k, int d,
+                     int dsub, int per_pair) {
+    IvfPqPlan P;
+    static_cast<IvfPlan&>(P) = plan_ivf(nq, nprobe_eff, nlist, max_list_rows, ntotal, k, 0);
+    const int64_t np = std::max(1, nprobe_eff);
+    if (dsub <= 0 || dsub % 8 != 0) P.path = IVF_PATH_EXACT;
+    const bool fused = P.path == IVF_PATH_FUSED;
+    const int64_t cand_q = (int64_t)P.slots * (fused ? KP : k) * 8;
+    // (plan_ivf sized q_batch for the fused lists; the exact path's are slots * k entries)
+    P.q_batch = std::max<int64_t>(1, std::min<int64_t>(std::max<int64_t>(nq, 1), IVF_CAND_BYTES / cand_q));
+    if (fused) {
+        // a query costs its operands (np, or one) and its lists; the padding costs < 128 operands
+        const int64_t op = 4 * (int64_t)pq_kpad(std::max(1, d));
+        const int64_t per_query = (per_pair ? np : 1) * op + cand_q;
+        const int64_t room = IVFPQ_PASS_BYTES - (TILE_Q - 1) * op;
+        P.q_batch = std::max<int64_t>(1, std::min<int64_t>(P.q_batch, room / per_query));
+        const int64_t bp = P.q_batch * np;
+        P.pairs_pad = (bp + TILE_Q - 1) / TILE_Q * TILE_Q;
+        P.op_rows = per_pair ? P.pairs_pad : (P.q_batch + TILE_Q - 1) / TILE_Q * TILE_Q;
+        P.plane_bytes = P.op_rows * op;
+    }
+    const int64_t bp = P.q_batch * np;
+    P.grid = (bp / TILE_Q + std::min<int64_t>(nlist, bp)) * P.chunks;
+    P.cand_bytes = P.q_batch * cand_q;
+    return P;
+}
+
 bool plan_remove(const KeptPrefix& P, int64_t stage_rows, std::vector<RemoveChunk>& out) {
     const int64_t g = P.g, nt = P.ntotal;
     const int64_t nb = (nt + g - 1) / g;  // boundary i is row min(nt, i g)

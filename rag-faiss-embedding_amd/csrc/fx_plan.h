@@ -119,6 +119,23 @@ constexpr int64_t IVFSQ_PASS_BYTES = 1ll << 30;
 IvfSqPlan plan_ivfsq(int64_t nq, int nprobe_eff, int64_t nlist, int64_t max_list_rows, int64_t ntotal, int k,
                      int row_bytes);
 
+// ---- inverted file over product-quantized codes (fx_ivfpq.hip): the plan of one IndexIVFPQ search
+
+// plan_ivfsq with the product quantizer's operands and one more reason for the exact path: path is
+// exact for k > KP and for every dsub that is no multiple of 8 (plan_pq's rule).  An operand is two
+// bf16 planes of kpad(d) = roundup(d, 32) values, 4 kpad(d) bytes; per_pair != 0 (L2 with by_residual)
+// there is one per (query, probe) pair, otherwise one per query.  q_batch keeps the operand planes
+// plus the candidate lists of a pass within IVFPQ_PASS_BYTES.
+struct IvfPqPlan : IvfPlan {
+    int64_t pairs_pad = 0;    // roundup(q_batch * nprobe_eff, 128)
+    int64_t op_rows = 0;      // plane rows of a full pass: pairs_pad, or roundup(q_batch, 128) (exact path: 0)
+    int64_t plane_bytes = 0;  // 2 * op_rows * kpad(d) * 2 (exact path: 0, it prepares no operand)
+    int64_t cand_bytes = 0;   // q_batch * slots * (KP or k) * 8
+};
+constexpr int64_t IVFPQ_PASS_BYTES = 1ll << 30;
+IvfPqPlan plan_ivfpq(int64_t nq, int nprobe_eff, int64_t nlist, int64_t max_list_rows, int64_t ntotal, int k, int d,
+                     int dsub, int per_pair);
+
 // ---- remove_ids (fx_remove.hip): the host's chunk plan ----------------------
 
 // Kept rows before row r, for the rows the plan asks about: any row (the

@@ -1,5 +1,5 @@
 // fx_sq_common.h -- device helpers the two 8-bit indexes share (fx_sq.hip, fx_ivfsq.hip; fx_pq.hip
-// takes the certification test): the
+// and fx_ivfpq.hip take the certification test, fx_ivfpq.hip the rounded addition too): the
 // codec's scalar encode / decode, the affine form of a table entry, the digit of a query
 // operand plane, the refine's certification test, and the stage layout of the int8 tile loop.
 #pragma once
@@ -13,6 +13,16 @@ constexpr int SQ_STAGE_BYTES = (TILE_R + SQ_P * TILE_Q) * SQ_STAGE_B;
 static_assert(2 * SQ_STAGE_BYTES == LDS_STAGE, "the int8 stages fill k_scan_topk's double buffer");
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// one rounded fp32 addition / subtraction that no neighbouring multiply is fused into
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
 
 // the decoded value of signed code cs: two rounded fp32 operations on the
 // table value (c + 0.5) / 255, bitwise a numpy fp32 expression

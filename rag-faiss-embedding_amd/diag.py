@@ -5,7 +5,7 @@ compiled under ``-DFX_DIAG`` (``make -C csrc diag``): its option table adds
 the test hooks the product library does not carry -- ``force_fallback``
 (1: every query through the device-gated re-scan, 2: through the exact fp64
 scan) and ``scan_dbg`` 32 (the scan's whole key matrix dumped to
-``FX_SCAN_KEYS``) -- plus the FX_SCAN_TRACE / _CAND dumps, and three dumps of
+``FX_SCAN_KEYS``) -- plus the FX_SCAN_TRACE / _CAND dumps, and the dumps of
 the newer scans' lists, written per pass before the refine reads them and the
 exact path writes over them (paths read when the index is created):
 
@@ -26,6 +26,13 @@ exact path writes over them (paths read when the index is created):
                  ``E`` [nq], the shift [nq] f64, the query planes [2][nq_pad][kp]
                  bf16 ([hi | lo]), the rows' codes [ntotal][roundup(M, 16)] u8 and
                  ``n_y`` [ntotal] (tests/test_pq_scan_parity.py)
+``FX_IVFPQ_CAND``  fx_ivfpq_search: ``cand_d``, ``cand_i`` [nq][slots][KP], the
+                 probed lists [nq][nprobe] i64, ``list_off`` [nlist + 1] i32, the
+                 pairs' shift and ``E`` [pairs_pad] f32 each, the operand planes
+                 [2][op_rows][kp] bf16 ([hi | lo]; op_rows = pairs_pad for L2 with
+                 by_residual, else roundup(nq, 128)), the rows' codes
+                 [ntotal][roundup(M, 16)] u8 and ``n_y`` [ntotal]
+                 (tests/test_ivfpq_scan_parity.py)
 
 The classes here are the faiss.py ones with every call going to that build.
 """
@@ -76,6 +83,16 @@ class IndexIVFFlat(_faiss.IndexIVFFlat):
 
 class IndexIVFScalarQuantizer(_faiss.IndexIVFScalarQuantizer):
     """As ``IndexIVFFlat`` above: a quantizer of this module.  ``FX_IVFSQ_CAND``
+    and ``FX_FORCE_FALLBACK`` come from the environment when the index is
+    created."""
+
+    def __init__(self, quantizer, *args, **kwargs):
+        assert quantizer._lib is lib, "the quantizer must be an index of the diagnostic build"
+        super().__init__(quantizer, *args, **kwargs)
+
+
+class IndexIVFPQ(_faiss.IndexIVFPQ):
+    """As ``IndexIVFFlat`` above: a quantizer of this module.  ``FX_IVFPQ_CAND``
     and ``FX_FORCE_FALLBACK`` come from the environment when the index is
     created."""
 

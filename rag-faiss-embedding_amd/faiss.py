@@ -1694,7 +1694,7 @@ class ProductQuantizer:
     def centroids(self) -> np.ndarray:
         ix = self._index
         out = np.empty(self.M * self.ksub * self.dsub, dtype=np.float32)
-        ix._check(ix._lib.fx_pq_get_centroids(ix._h, out.ctypes.data_as(ctypes.c_void_p)))
+        ix._check(ix._fn("get_centroids")(ix._h, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
     @centroids.setter
@@ -1703,7 +1703,7 @@ class ProductQuantizer:
         a = np.ascontiguousarray(arr, dtype=np.float32).reshape(-1)
         assert a.size == self.M * self.ksub * self.dsub, f"centroids must hold {self.M * self.ksub * self.dsub} floats"
         assert ix.ntotal == 0, "centroids set on an index that holds rows: reset() it first"
-        ix._check(ix._lib.fx_pq_set_centroids(ix._h, a.ctypes.data_as(ctypes.c_void_p)))
+        ix._check(ix._fn("set_centroids")(ix._h, a.ctypes.data_as(ctypes.c_void_p)))
 
 
 class IndexPQ(_CodeIndex):
@@ -1916,9 +1916,136 @@ class IndexIVFScalarQuantizer(IndexIVFFlat):
         return out
 
 
+# ---------------------------------------------------------------------------
+# faiss.IndexIVFPQ (include/fx_index.h "inverted file over product-quantized codes")
+# ---------------------------------------------------------------------------
+class IndexIVFPQ(IndexIVFFlat):
+    """``faiss.IndexIVFPQ(quantizer, d, nlist, M, nbits, metric)`` with 8-bit
+    codes: ``IndexIVFFlat``'s lists holding ``IndexPQ``'s rows, M bytes each.
+    With ``by_residual`` (faiss's default) a row of list l is encoded as ``x -
+    c_l`` and decodes to ``c_l + decode(code)``, so the codebook covers a
+    cluster, not the corpus.  A search ranks the DECODED rows of the probed
+    lists exactly: ids bit-exact, distances the fp64 sum rounded once, ranked
+    by (distance, list number, insertion order within the list).
+
+    The definition restates faiss's from memory and is not checked against a
+    faiss build; in particular faiss ranks a row by the distance between the
+    query's residual and the decoded residual, this class by the decoded row.
+
+    ``pq`` is the ``ProductQuantizer`` view of the codebook (``pq.centroids``
+    get and set).  ``train(x)`` trains the coarse quantizer as
+    ``IndexIVFFlat.train`` does if it is untrained, then M times ``Kmeans(dsub,
+    256, niter=pq_niter, seed)`` on the slices of the residuals of ``x``.
+
+    Not offered: ``nbits != 8`` (``NotImplementedError``), precomputed tables,
+    polysemous search, OPQ, fast-scan, selectors, ``remove_ids``,
+    ``range_search``, ``reconstruct*``, ``write_index`` / ``read_index``."""
+
+    _PFX = "fx_ivfpq_"
+
+    def __init__(self, quantizer, d: int, nlist: int, M: int, nbits: int = 8, metric: int = METRIC_L2,
+                 by_residual: bool = True, device: int = 0, niter: int = 10, seed: int = 1234, pq_niter: int = 25):
+        d, M, nbits = int(d), int(M), int(nbits)
+        if nbits != 8:
+            raise NotImplementedError(f"IndexIVFPQ: nbits = {nbits} is not offered (8)")
+        if d <= 0 or M <= 0 or d % M != 0:
+            raise ValueError(f"IndexIVFPQ: d = {d} is not a multiple of M = {M}")
+        assert isinstance(quantizer, _FlatIndex), "quantizer must be an IndexFlatL2 / IndexFlatIP of this module"
+        assert quantizer.d == d, f"quantizer has d = {quantizer.d}, the index d = {d}"
+        assert quantizer.device == int(device), f"quantizer on cuda:{quantizer.device}, index on cuda:{int(device)}"
+        assert metric in (METRIC_L2, METRIC_INNER_PRODUCT), "metric must be METRIC_L2 or METRIC_INNER_PRODUCT"
+        self.quantizer = quantizer
+        self._lib = quantizer._lib
+        self._d, self.nlist, self.metric_type = d, int(nlist), int(metric)
+        self.by_residual = bool(by_residual)
+        self.storage_dtype, self.device = "uint8", int(device)
+        self.nprobe = 1
+        self.niter, self.seed = int(niter), int(seed)
+        self.verbose = False
+        self._mode = None
+        self.pq = ProductQuantizer(self, d, M, nbits, pq_niter, seed)
+        self._h = ctypes.c_void_p()
+        self._check(self._fn("create")(quantizer._h, d, self.nlist, M, nbits, self.metric_type,
+                                       1 if self.by_residual else 0, ctypes.byref(self._h)))
+
+    @property
+    def code_size(self) -> int:
+        return self.pq.M
+
+    @property
+    def is_trained(self) -> bool:
+        if self.quantizer.ntotal != self.nlist:
+            return False
+        v = ctypes.c_int(0)
+        self._check(self._fn("is_trained")(self._h, ctypes.byref(v)))
+        return bool(v.value)
+
+    _rows = _rows
+
+    def _residuals(self, x):
+        """A device tensor ``[n][d]`` fp32 of the residuals of the rows ``x``
+        (numpy or a device tensor), through ``fx_ivfpq_residuals``."""
+        t = _torch()
+        ptr, code, mem, n, _keep = self._rows(x)
+        self._bind_stream(True)  # (the output is a tensor of the current stream)
+        out = t.empty((n, self._d), dtype=t.float32, device=t.device("cuda", self.device))
+        self._check(self._fn("residuals")(self._h, n, ptr, code, mem, ctypes.c_void_p(out.data_ptr()), _lib.MEM_DEVICE))
+        return out
+
+    def train(self, x) -> None:
+        """k-means on the quantizer if it holds no centroids yet (as
+        ``IndexIVFFlat.train``), then the codebook: the residuals of ``x``
+        (numpy rows, a device tensor, or a flat index of this module, its
+        stored rows gathered chunk by chunk) are computed on the device, and
+        ``Kmeans(dsub, 256, niter=pq.niter, seed=pq.seed)`` runs on the slice
+        of every sub-quantizer; the centroids are installed as
+        ``pq.centroids``.  A no-op on a trained index, as faiss.  Fewer than
+        256 rows is an error."""
+        if self.is_trained:
+            return
+        assert self.ntotal == 0, "train on an index that holds rows: reset() it first"
+        if self.quantizer.ntotal != self.nlist:
+            IndexIVFFlat.train(self, x)
+        t = _torch()
+        pq = self.pq
+        flat = _flat(x) if _is_index(x) else None
+        if flat is not None:
+            assert not flat.has_ids and flat.device == self.device and flat.d == self._d
+        n = flat.ntotal if flat is not None else int(x.shape[0])
+        if n < pq.ksub:
+            raise RuntimeError(f"IndexIVFPQ.train: {n} training rows, fewer than the {pq.ksub} centroids of a "
+                               f"sub-quantizer")
+        chunks = []
+        for r0 in range(0, n, KMEANS_CHUNK):
+            if flat is not None:
+                keys = t.arange(r0, min(n, r0 + KMEANS_CHUNK), dtype=t.int64, device=t.device("cuda", self.device))
+                chunks.append(self._residuals(flat.reconstruct_batch(keys + flat._id_offset, dtype="storage")))
+            else:
+                chunks.append(self._residuals(x[r0:r0 + KMEANS_CHUNK]))
+        cents = np.empty((pq.M, pq.ksub, pq.dsub), dtype=np.float32)
+        for m in range(pq.M):
+            km = Kmeans(pq.dsub, pq.ksub, niter=pq.niter, seed=pq.seed, device=self.device)
+            km.train(t.cat([c[:, m * pq.dsub:(m + 1) * pq.dsub] for c in chunks]).contiguous())
+            cents[m] = km.centroids
+        pq.centroids = cents
+
+    def get_list_codes(self, l: int) -> np.ndarray:
+        """The codes of list ``l`` in insertion order: ``(n, M)`` uint8."""
+        n = ctypes.c_int64(0)
+        self._check(self._fn("list_codes")(self._h, int(l), None, 0, ctypes.byref(n)))
+        out = np.empty((n.value, self.pq.M), dtype=np.uint8)
+        if n.value:
+            self._check(self._fn("list_codes")(self._h, int(l), out.ctypes.data_as(ctypes.c_void_p), n.value,
+                                               ctypes.byref(n)))
+        return out
+
+
 def write_index(index, path: str) -> None:
     """``faiss.write_index`` (faiss_store.py:91): IxF2 file, fp32 codes; a
     labelled index (``IndexIDMap`` / ``IndexIDMap2``) as an IxM2 file."""
+    if isinstance(index, IndexIVFPQ):
+        raise NotImplementedError("write_index of an IndexIVFPQ: write its quantizer, keep `pq.centroids` with numpy "
+                                  "and re-add the rows")
     if isinstance(index, IndexIVFScalarQuantizer):
         raise NotImplementedError("write_index of an IndexIVFScalarQuantizer: write its quantizer, keep `trained` "
                                   "with numpy and re-add the rows")

@@ -32,7 +32,7 @@ class FAISSVectorStore:
 
     _instance = None
     _initialized = False
-    ivf = None  # the IndexIVFFlat / IndexIVFScalarQuantizer over the store's rows (build_ivf); dropped by every
+    ivf = None  # the IndexIVFFlat / IndexIVFScalarQuantizer / IndexIVFPQ over the store's rows (build_ivf); dropped by every
                 # call that changes the rows
     sq = None   # the IndexScalarQuantizer over the store's rows (build_sq); dropped by the same calls
     pq = None   # the IndexPQ over the store's rows (build_pq); dropped by the same calls
@@ -79,7 +79,7 @@ class FAISSVectorStore:
         rows = [r for r, doc in enumerate(self.doc_ids) if doc in allowed]
         return _fx.SearchParameters(sel=_fx.IDSelectorBatch(np.asarray(rows, dtype=np.int64)))
 
-    def build_ivf(self, nlist: int, nprobe: int = 8, qtype=None):
+    def build_ivf(self, nlist: int, nprobe: int = 8, qtype=None, pq_m=None):
         """An ``IndexIVFFlat`` over the store's rows (extension): the coarse
         quantizer is trained on the store's own index, so the rows never leave
         the GPU, and the rows are added with ids equal to their row numbers, so
@@ -88,11 +88,19 @@ class FAISSVectorStore:
         (``ScalarQuantizer.QT_8bit`` / ``QT_8bit_uniform``) the lists hold one
         byte per dimension instead: an ``IndexIVFScalarQuantizer`` with
         residual encoding, searched the same way (the k nearest DECODED rows
-        of the probed lists).  Errors are logged and raised again, as in
+        of the probed lists).  With ``pq_m = M`` the lists hold M bytes per
+        row: an ``IndexIVFPQ`` with residual encoding, trained on the store's
+        rows and searched the same way.  ``qtype`` and ``pq_m`` together are a
+        ``ValueError``.  Errors are logged and raised again, as in
         ``load_index``."""
+        if qtype is not None and pq_m is not None:
+            raise ValueError("build_ivf: qtype and pq_m name two different list encodings; pass one")
         try:
             quantizer = _fx.IndexFlatL2(self.dimension, device=self.device)
-            if qtype is None:
+            if pq_m is not None:
+                ivf = _fx.IndexIVFPQ(quantizer, self.dimension, int(nlist), int(pq_m), 8, _fx.METRIC_L2,
+                                     device=self.device)
+            elif qtype is None:
                 ivf = _fx.IndexIVFFlat(quantizer, self.dimension, int(nlist), _fx.METRIC_L2, dtype=self.dtype,
                                        device=self.device)
             else:
